@@ -4,6 +4,7 @@ committee=4096 (BASELINE.json configs[1]: "4096-key G1 pubkey MSM + single
 pairing verify on 1 MI355X"), batched.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+                  [--dump-outputs DIR] [--full]
 
 One "step" = one hbls_batch_agg_verify of B independent aggregate-verifies
 (distinct seeded messages, Bernoulli(0.9) masks) against a device-resident
@@ -11,8 +12,22 @@ One "step" = one hbls_batch_agg_verify of B independent aggregate-verifies
 per GPU; per-shard committees are independent (BASELINE configs[2]) — no
 data-path collective, weak scaling; value = whole-job verifies/sec.
 
-Requires an MI355X: the product path has no CPU fallback.  The cpu_baseline
-leg times the CPU oracle (restatement, "port") on the same box.
+A plain run does only what the headline figure needs: build the seeded
+inputs, warm up, time K steps, print one JSON result line.  The verdicts of
+the last timed step are checked after the clock stops (every item must
+verify).  --full adds the legs that take runs of their own: the pre-timing
+correctness gate, the roofline leg (measured VALU peak µbench) and the
+cpu_baseline leg, which times the CPU oracle (restatement, "port") on the
+same box.  Without --full the result line carries roofline/cpu_baseline as
+null.
+
+--dump-outputs DIR writes what the timed path returned in its last timed
+step as DIR/<name>.npy (float32): verify_results (one verdict per item;
+config2 and config4), round_bitmaps + round_agg_sigs (stream mode: the last
+batch's per-round state, byte values).  Inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
+
+Requires an MI355X: the product path has no CPU fallback.
 """
 import argparse
 import json
@@ -32,6 +47,36 @@ MAD64_PER_FPMUL = 72   # CIOS 6x64: 6 iterations x (6 mul-acc + 6 reduce mul-acc
 def log(msg):
     if int(os.environ.get("RANK", "0")) == 0:
         print(msg, file=sys.stderr, flush=True)
+
+
+DUMP_CAP_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: write each named output of the last timed step as
+    outdir/<name>.npy (float32).  An output too large for its share of the
+    64 MB cap is written as a fixed seeded sample of its flattened elements
+    (same indices every run, so dumps stay comparable)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    cap = DUMP_CAP_BYTES // (4 * max(1, len(arrays)))   # elements per array
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
+def _rank_name(name, rank, world):
+    """every rank dumps its own shard's outputs; single-rank names stay bare"""
+    return name if world == 1 else f"{name}_rank{rank}"
+
+
+def _bytes_rows(buf, width):
+    """serialized device output (bytes) -> [rows, width] array of byte values"""
+    import numpy as np
+    return np.frombuffer(buf, dtype=np.uint8).reshape(-1, width)
 
 
 def _rand_bits(rng, rows, cols, p):
@@ -174,8 +219,9 @@ def run_config4(args, rank, world, dist):
         one_step(False)
     barrier_sync()
     t0 = time.perf_counter()
+    res = []
     for _ in range(args.steps):
-        one_step(False)
+        res = one_step(False)
     barrier_sync()
     t1 = time.perf_counter()
     elapsed = t1 - t0
@@ -184,6 +230,8 @@ def run_config4(args, rank, world, dist):
                          device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {_rank_name("verify_results", rank, world): res})
     if rank != 0:
         return
     value = args.steps * batch / elapsed
@@ -276,6 +324,12 @@ def run_stream(args):
     if not msv.final_check_collect():       # last batch's pipelined check
         print(json.dumps({"error": "stream pipelined aggregate diverged"}))
         sys.exit(1)
+    if args.dump_outputs:
+        # the last batch's per-round state: signer bitmaps + running aggregates
+        state = [msv.stream.get(r) for r in range(R)]
+        dump_outputs(args.dump_outputs, {
+            "round_bitmaps": _bytes_rows(b"".join(s[0] for s in state), (n + 7) // 8),
+            "round_agg_sigs": _bytes_rows(b"".join(s[1] for s in state), 96)})
     value = total_msgs / t_all
     print(json.dumps({
         "metric": "FBFT streaming vote messages/sec (committee=256, per-msg verify + incremental aggregate)",
@@ -303,8 +357,18 @@ def main():
                     help="config2: per-rank replica committees (default, weak scaling); "
                          "config4: one 65536-key committee sharded across ranks with "
                          "partial-sum all-gather over RCCL")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave out the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the "
+                         "pre-timing correctness gate, the roofline leg (VALU "
+                         "peak µbench) and the CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as "
+                         "DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 and args.mode != "stream":
+        ap.error("--steps must be at least 1 (ms_per_step divides by it)")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -354,12 +418,18 @@ def main():
     msgs_cat = b"".join(msgs)
     sigs = core.batch_sign(sk_sum_bytes, msgs_cat, MSG_LEN, args.batch)
 
-    # correctness gate before timing: every item must verify
-    res = committee.batch_agg_verify(bitmaps_cat, sigs, msgs_cat, MSG_LEN, args.batch)
-    bad = [i for i, r in enumerate(res) if r != 1]
-    if bad:
-        print(json.dumps({"error": f"verify gate failed on items {bad[:5]}"}))
-        sys.exit(1)
+    def gate(res, what):
+        """every item must verify"""
+        bad = [i for i, r in enumerate(res) if r != 1]
+        if bad:
+            print(json.dumps({"error": f"{what} failed on items {bad[:5]}"}))
+            sys.exit(1)
+
+    # correctness gate before timing (a run of its own: --full only; a plain
+    # run gates on the verdicts of its last timed step instead, below)
+    if args.full:
+        gate(committee.batch_agg_verify(bitmaps_cat, sigs, msgs_cat, MSG_LEN, args.batch),
+             "verify gate")
 
     def barrier_sync():
         if dist is not None:
@@ -375,7 +445,7 @@ def main():
     stage_ns = [0, 0, 0, 0]
     pipe_ns = 0
     for _ in range(args.steps):
-        committee.batch_agg_verify(bitmaps_cat, sigs, msgs_cat, MSG_LEN, args.batch)
+        res = committee.batch_agg_verify(bitmaps_cat, sigs, msgs_cat, MSG_LEN, args.batch)
         pipe_ns += core.last_kernel_ns()
         for i in range(4):
             stage_ns[i] += core._lib.hbls_last_stage_ns(i)
@@ -395,6 +465,11 @@ def main():
     value = total_verifies / elapsed
     ms_per_step = elapsed / args.steps * 1e3
 
+    # the timed path's own output: the verdicts of the last timed step
+    gate(res, "timed-step verify")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {_rank_name("verify_results", rank, world): res})
+
     if rank != 0:
         return
 
@@ -405,7 +480,8 @@ def main():
     # than the GPU path (oracle 54,358 vs GPU 37,044 per aggregate-verify at
     # this config) and overstated `achieved`; these are the honest GPU-side
     # constants for committee=4096 Bernoulli(0.9) masks.
-    oc = capi.Committee(pks, COMMITTEE)      # oracle committee (cpu_baseline)
+    want_cpu = args.full and not args.skip_cpu_baseline
+    oc = capi.Committee(pks, COMMITTEE) if want_cpu else None   # oracle committee
     f_mask = 3829
     f_hash = 7007
     f_decompress = 4306
@@ -414,7 +490,8 @@ def main():
     f_total = 37044
 
     # ---- roofline: dominant stage = k_verify (pairing); live HIP-event time
-    peak = core._lib.hbls_mad_peak_ops()
+    # (--full only: the peak is a µbench launch of its own)
+    peak = core._lib.hbls_mad_peak_ops() if args.full else 0.0
     verify_stage_s = stage_ns[3] / 1e9 / args.steps     # per launch (B items)
     ach = (f_verify_stage * MAD64_PER_FPMUL * args.batch) / verify_stage_s if verify_stage_s else 0
     roofline = {
@@ -438,6 +515,8 @@ def main():
                                "verify_stage": f_verify_stage, "total": f_total,
                                "source": "GPU-instrumented (r2d_mulcounts)"},
     }
+    if not args.full:
+        roofline = None
 
     # ---- CPU baseline: the oracle ("port"), OpenMP over items.  Two-phase:
     # a short probe sizes a ~12s sustained sample (tier rule: 10-30s of CPU
@@ -445,7 +524,7 @@ def main():
     # CPUs) bind the way they would in any sustained run — burst-sized
     # samples overstate the rate.  Thread count pinned at main() start.
     cpu_baseline = None
-    if not args.skip_cpu_baseline:
+    if want_cpu:
         cores = capi.nthreads()
         probe = max(32 * cores, 64)
         reps0 = (probe + args.batch - 1) // args.batch
