@@ -244,36 +244,109 @@ DEVN void fp_from_mont(uint64_t raw[6], const fp_t &x) {
 #pragma unroll
     for (int i = 0; i < 6; i++) raw[i] = t.l[i];
 }
-/* exponentiation, exponent = LE limb array (plain integer) */
-DEVN void fp_pow(fp_t &r, const fp_t &a, const uint64_t *e, int n) {
-    fp_t acc;
-    fp_one(acc);
-    bool started = false;
-    for (int i = n - 1; i >= 0; i--)
-        for (int b = 63; b >= 0; b--) {
-            if (started) fp_sqr_inl(acc, acc);
-            if ((e[i] >> b) & 1) {
-                if (started) fp_mul_inl(acc, acc, a);
-                else { acc = a; started = true; }
-            }
-        }
-    r = acc;
+/* s = x^((p-3)/4): the one exponentiation behind sqrt, legendre and inverse
+ * (p = 3 mod 4).  (p-3)/4 = p >> 2, so bit k of p drives step k-2; bit 380
+ * is p's top bit.  With c = s*x: c^2 = x iff x is a square, and then
+ * 1/c = s — a root and its inverse from one chain (fp2_sqrt_tail). */
+#ifdef HBLS_POW_BINARY
+DEVN void fp_pow_pm3o4(fp_t &s, const fp_t &x) {
+    fp_t acc = x;
+    for (int k = 379; k >= 2; k--) {
+        fp_sqr_inl(acc, acc);
+        if ((BLS_P[k >> 6] >> (k & 63)) & 1) fp_mul_inl(acc, acc, x);
+    }
+    s = acc;
 }
-DEVN void fp_inv(fp_t &r, const fp_t &x) { fp_pow(r, x, BLS_PM2, 6); }
+#else
+/* Sliding-window schedule for the fixed exponent, derived from the modulus
+ * at compile time: 4-bit windows over the odd powers x^1..x^15.  Entry i
+ * says "square nsq[i] times, then multiply by tab[idx[i]]"; idx 8 means no
+ * multiply (the exponent's trailing zero bits).  461 fp-mul against 570 for
+ * the binary chain (-DHBLS_POW_BINARY keeps that one for A/Bs); one shared
+ * inlined squaring and one inlined multiply, the 8 table entries through
+ * the called fp_mul. */
+#define POW_WIN 4
+#define POW_NOMUL (1 << (POW_WIN - 1))
+struct pow_sched_t { uint8_t nsq[128], idx[128]; int n, first; };
+/* BLS_P again, as a constexpr (the generated header's copy is a plain const
+ * array, which a constant expression may not read) */
+static constexpr uint64_t POW_P[6] = { 0xb9feffffffffaaabULL, 0x1eabfffeb153ffffULL, 0x6730d2a0f6b0f624ULL, 0x64774b84f38512bfULL, 0x4b1ba7b6434bacd7ULL, 0x1a0111ea397fe69aULL };
+constexpr int pm3o4_bit(int k) { return (int)((POW_P[(k + 2) >> 6] >> ((k + 2) & 63)) & 1); }
+constexpr pow_sched_t pm3o4_sched() {
+    pow_sched_t s{};
+    int k = 378, pending = 0;
+    bool first = true;
+    while (k >= 0) {
+        if (!pm3o4_bit(k)) { pending++; k--; continue; }
+        int l = k - (POW_WIN - 1) < 0 ? 0 : k - (POW_WIN - 1);
+        while (!pm3o4_bit(l)) l++;
+        int v = 0;
+        for (int j = k; j >= l; j--) v = 2 * v + pm3o4_bit(j);
+        if (first) { s.first = v >> 1; first = false; }
+        else { s.nsq[s.n] = (uint8_t)(pending + k - l + 1); s.idx[s.n] = (uint8_t)(v >> 1); s.n++; }
+        pending = 0;
+        k = l - 1;
+    }
+    if (pending) { s.nsq[s.n] = (uint8_t)pending; s.idx[s.n] = POW_NOMUL; s.n++; }
+    return s;
+}
+static constexpr pow_sched_t PM3O4 = pm3o4_sched();
+DEVN void fp_pow_pm3o4(fp_t &s, const fp_t &x) {
+    fp_t tab[POW_NOMUL], x2, acc;
+    tab[0] = x;
+    fp_sqr(x2, x);
+    for (int i = 1; i < POW_NOMUL; i++) fp_mul(tab[i], tab[i - 1], x2);
+    acc = tab[PM3O4.first];
+    for (int i = 0; i < PM3O4.n; i++) {
+        for (int j = PM3O4.nsq[i]; j > 0; j--) fp_sqr_inl(acc, acc);
+        if (PM3O4.idx[i] != POW_NOMUL) fp_mul_inl(acc, acc, tab[PM3O4.idx[i]]);
+    }
+    s = acc;
+}
+#endif
+/* x^(p-2) = s^4 x */
+DEVN void fp_inv(fp_t &r, const fp_t &x) {
+    fp_t s;
+    fp_pow_pm3o4(s, x);
+    fp_sqr(s, s);
+    fp_sqr(s, s);
+    fp_mul(r, s, x);
+}
+/* x^((p+1)/4) = s x, then check */
 DEVN bool fp_sqrt(fp_t &r, const fp_t &x) {
     fp_t y, y2;
-    fp_pow(y, x, BLS_SQRT_EXP, 6);
+    fp_pow_pm3o4(y, x);
+    fp_mul(y, y, x);
     fp_sqr(y2, y);
     if (!fp_eq(y2, x)) return false;
     r = y;
     return true;
 }
+/* x^((p-1)/2) = s^2 x */
 DEVN int fp_legendre(const fp_t &x) {
     if (fp_is_zero(x)) return 0;
     fp_t y, one;
-    fp_pow(y, x, BLS_LEG_EXP, 6);
+    fp_pow_pm3o4(y, x);
+    fp_sqr(y, y);
+    fp_mul(y, y, x);
     fp_one(one);
     return fp_eq(y, one) ? 1 : -1;
+}
+/* x/2: add p when odd, shift right (x + p < 2^382, no carry out).  Holds on
+ * Montgomery form unchanged. */
+DEV void fp_half(fp_t &r, const fp_t &x) {
+    uint64_t t[6];
+    const uint64_t m = 0 - (x.l[0] & 1);
+    u128 c = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        c += (u128)x.l[i] + (BLS_P[i] & m);
+        t[i] = (uint64_t)c;
+        c >>= 64;
+    }
+#pragma unroll
+    for (int i = 0; i < 5; i++) r.l[i] = (t[i] >> 1) | (t[i + 1] << 63);
+    r.l[5] = t[5] >> 1;
 }
 DEVN bool fp_is_odd(const fp_t &x) {
     uint64_t raw[6];
@@ -307,6 +380,7 @@ DEV void fp2_sub(fp2_t &r, const fp2_t &x, const fp2_t &y) { fp_sub(r.a, x.a, y.
 DEV void fp2_neg(fp2_t &r, const fp2_t &x) { fp_neg(r.a, x.a); fp_neg(r.b, x.b); }
 DEV void fp2_conj(fp2_t &r, const fp2_t &x) { r.a = x.a; fp_neg(r.b, x.b); }
 DEV void fp2_dbl(fp2_t &r, const fp2_t &x) { fp2_add(r, x, x); }
+DEV void fp2_half(fp2_t &r, const fp2_t &x) { fp_half(r.a, x.a); fp_half(r.b, x.b); }
 DEVN void fp2_mul(fp2_t &r, const fp2_t &x, const fp2_t &y) {
 #ifdef HBLS_FP2_RS
     /* compact-code variant: ~400-instr body + calls into the shared
@@ -376,6 +450,30 @@ DEVN void fp2_inv(fp2_t &r, const fp2_t &x) {
 }
 DEV void fp2_one(fp2_t &r) { fp_one(r.a); fp_zero(r.b); }
 DEV void fp2_zero(fp2_t &r) { fp_zero(r.a); fp_zero(r.b); }
+/* b != 0 half of fp2_sqrt, given w = sqrt(a^2 + b^2): t = (a+w)/2, else
+ * (a-w)/2; c = sqrt t; d = b/(2c).  t != 0 because b != 0, so with
+ * s = t^((p-3)/4) and c = s t, c^2 = t gives 1/c = s and d = b s / 2: one
+ * exponentiation per attempt and no inversion. */
+DEVN bool fp2_sqrt_tail(fp2_t &r, const fp2_t &x, const fp_t &w) {
+    fp_t t, s, c, c2, d;
+    fp_add(t, x.a, w);
+    fp_half(t, t);
+    fp_pow_pm3o4(s, t);
+    fp_mul(c, s, t);
+    fp_sqr(c2, c);
+    if (!fp_eq(c2, t)) {
+        fp_sub(t, x.a, w);
+        fp_half(t, t);
+        fp_pow_pm3o4(s, t);
+        fp_mul(c, s, t);
+        fp_sqr(c2, c);
+        if (!fp_eq(c2, t)) return false;
+    }
+    fp_mul(d, x.b, s);
+    fp_half(d, d);
+    r.a = c; r.b = d;
+    return true;
+}
 DEVN bool fp2_sqrt(fp2_t &r, const fp2_t &x) {
     if (fp_is_zero(x.b)) {
         fp_t s, na;
@@ -384,26 +482,38 @@ DEVN bool fp2_sqrt(fp2_t &r, const fp2_t &x) {
         if (fp_sqrt(s, na)) { fp_zero(r.a); r.b = s; return true; }
         return false;
     }
-    fp_t n, t, w, c, d, inv2, two, t2;
+    fp_t n, t, w;
     fp_sqr(n, x.a);
     fp_sqr(t, x.b);
     fp_add(n, n, t);
     if (!fp_sqrt(w, n)) return false;
-    /* inv2 = 2^-1 */
-    fp_one(two);
-    fp_dbl(two, two);
-    fp_inv(inv2, two);
+    return fp2_sqrt_tail(r, x, w);
+}
+/* Either root of x, for callers that fix the sign afterwards by parity
+ * (g2_deserialize).  Same accept/reject as fp2_sqrt; the b != 0 path needs
+ * no second attempt: with t = (a+w)/2, s = t^((p-3)/4), c = s t, c^2 is t
+ * or -t.  If -t, then t' = (a-w)/2 = -b^2/(4t) is the square, s^2 = -1/t
+ * and s c = -1, so (b s / 2, -c) is a root: its square is
+ * (t' + t) + (-b s c) u = a + b u.  Both components are non-zero on this
+ * path, so the parity of the result decides the sign. */
+DEVN bool fp2_sqrt_any(fp2_t &r, const fp2_t &x) {
+    if (fp_is_zero(x.b)) return fp2_sqrt(r, x);
+    fp_t n, t, w, s, c, c2, d;
+    fp_sqr(n, x.a);
+    fp_sqr(t, x.b);
+    fp_add(n, n, t);
+    if (!fp_sqrt(w, n)) return false;
     fp_add(t, x.a, w);
-    fp_mul(t, t, inv2);
-    if (!fp_sqrt(c, t)) {
-        fp_sub(t, x.a, w);
-        fp_mul(t, t, inv2);
-        if (!fp_sqrt(c, t)) return false;
-    }
-    fp_dbl(t2, c);
-    fp_inv(t2, t2);
-    fp_mul(d, x.b, t2);
-    r.a = c; r.b = d;
+    fp_half(t, t);
+    fp_pow_pm3o4(s, t);
+    fp_mul(c, s, t);
+    fp_sqr(c2, c);
+    fp_mul(d, x.b, s);
+    fp_half(d, d);
+    if (fp_eq(c2, t)) { r.a = c; r.b = d; return true; }
+    fp_neg(c2, c2);
+    if (!fp_eq(c2, t)) return false;
+    r.a = d; fp_neg(r.b, c);
     return true;
 }
 DEV bool fp2_is_odd(const fp2_t &x) { return fp_is_odd(x.a); }
@@ -737,7 +847,7 @@ DEVN bool g2_deserialize(g2_t &p, const uint8_t in[96], bool check_subgroup) {
     fp2_sqr(y2, a.x); fp2_mul(y2, y2, a.x);
     g2_b(b);
     fp2_add(y2, y2, b);
-    if (!fp2_sqrt(a.y, y2)) return false;
+    if (!fp2_sqrt_any(a.y, y2)) return false;
     if (fp2_is_odd(a.y) != odd) fp2_neg(a.y, a.y);
     g2_from_affine(p, a);
     if (check_subgroup && !g2_in_subgroup_fast(p)) return false;
@@ -745,47 +855,67 @@ DEVN bool g2_deserialize(g2_t &p, const uint8_t in[96], bool check_subgroup) {
 }
 
 /* ================================================================ FT map + cofactor */
+/* 1/c1^2 = -1/3 (Montgomery form) */
+static const uint64_t FT_NEG_INV3[6] = { 0x6bfcaaaaaaa98e3aULL, 0x10e7fffba46d5554ULL, 0xad4d68c3364ddf23ULL, 0xa43851108110e928ULL, 0xa506d9b4e0519578ULL, 0x0158e66214ffab57ULL };
 DEVN bool ft_map_g2(g2aff_t &r, const fp2_t &t) {
     if (fp2_is_zero(t)) return false;
-    fp_t norm, tmp;
-    fp_sqr(norm, t.a);
-    fp_sqr(tmp, t.b);
-    fp_add(norm, norm, tmp);
-    bool neg = fp_legendre(norm) < 0;
-    fp2_t w, b2, x, y2, y;
-    g2_b(b2);
-    fp2_sqr(w, t);
-    fp2_add(w, w, b2);
-    { fp_t one; fp_one(one); fp_add(w.a, w.a, one); }
-    if (fp2_is_zero(w)) return false;
-    fp2_inv(w, w);
-    fp2_mul(w, w, t);
-    { fp_t c1; fp_load(c1, BLS_FT_C1); fp2_mul_fp(w, w, c1); }
-    for (int i = 0; i < 3; i++) {
-        if (i == 0) {
-            fp2_mul(x, t, w);
-            fp2_neg(x, x);
-            fp_t c2; fp_load(c2, BLS_FT_C2);
-            fp_add(x.a, x.a, c2);
-        } else if (i == 1) {
-            fp2_neg(x, x);
-            fp_t one; fp_one(one);
-            fp_sub(x.a, x.a, one);
-        } else {
-            fp2_sqr(x, w);
-            fp2_inv(x, x);
-            fp_t one; fp_one(one);
-            fp_add(x.a, x.a, one);
-        }
-        fp2_sqr(y2, x); fp2_mul(y2, y2, x);
-        fp2_add(y2, y2, b2);
-        if (fp2_sqrt(y, y2)) {
-            if (neg) fp2_neg(y, y);
-            r.x = x; r.y = y;
-            return true;
-        }
+    /* neg = legendre(norm t) < 0.  For t in Fp (what hash_to_g2_point feeds)
+     * the norm is a non-zero square: no exponentiation. */
+    bool neg = false;
+    if (!fp_is_zero(t.b)) {
+        fp_t norm, tmp;
+        fp_sqr(norm, t.a);
+        fp_sqr(tmp, t.b);
+        fp_add(norm, norm, tmp);
+        neg = fp_legendre(norm) < 0;
     }
-    return false;
+    /* Thread-per-item: a wave pays for every lane's path, so the control
+     * flow is kept uniform.  One inversion of w0*t serves 1/w0 and 1/t
+     * (x3 = 1 + 1/w^2 = 1 + w0^2 (1/t)^2 / c1^2, c1^2 = -3); each candidate
+     * gets one norm-sqrt attempt in order x1 -> x2 -> x3; the sqrt tail
+     * runs once, on the chosen candidate.  Same field elements as the
+     * candidate-by-candidate fp2_sqrt form. */
+    fp2_t tt, w0, iv, w, b2, xc[3], x, y2, y;
+    fp_t one, wn;
+    fp_one(one);
+    g2_b(b2);
+    fp2_sqr(tt, t);
+    fp2_add(w0, tt, b2);
+    fp_add(w0.a, w0.a, one);
+    if (fp2_is_zero(w0)) return false;
+    fp2_mul(iv, w0, t);
+    fp2_inv(iv, iv);                              /* 1/(w0 t) */
+    fp2_mul(w, iv, tt);                           /* t/w0 */
+    { fp_t c1; fp_load(c1, BLS_FT_C1); fp2_mul_fp(w, w, c1); }
+    fp2_mul(x, t, w);
+    fp2_neg(xc[0], x);
+    { fp_t c2; fp_load(c2, BLS_FT_C2); fp_add(xc[0].a, xc[0].a, c2); }
+    fp2_neg(xc[1], xc[0]);
+    fp_sub(xc[1].a, xc[1].a, one);
+    fp2_sqr(x, w0);
+    fp2_mul(x, x, iv);                            /* w0/t */
+    fp2_sqr(x, x);
+    { fp_t c; fp_load(c, FT_NEG_INV3); fp2_mul_fp(xc[2], x, c); }
+    fp_add(xc[2].a, xc[2].a, one);
+    bool found = false;
+    for (int i = 0; i < 3; i++) {
+        if (found) continue;
+        fp2_t xi = xc[i], g;
+        fp_t n, u;
+        fp2_sqr(g, xi); fp2_mul(g, g, xi);
+        fp2_add(g, g, b2);
+        fp_sqr(n, g.a);
+        fp_sqr(u, g.b);
+        fp_add(n, n, u);
+        if (fp_sqrt(u, n)) { found = true; x = xi; y2 = g; wn = u; }
+    }
+    if (!found) return false;
+    /* b == 0 (negligible) keeps fp2_sqrt's own path */
+    bool ok = fp_is_zero(y2.b) ? fp2_sqrt(y, y2) : fp2_sqrt_tail(y, y2, wn);
+    if (!ok) return false;
+    if (neg) fp2_neg(y, y);
+    r.x = x; r.y = y;
+    return true;
 }
 DEV void g2_mul_u64(g2_t &r, const g2_t &p, uint64_t k) { g2_mul(r, p, &k, 1); }
 DEVN void g2_clear_cofactor(g2_t &r, const g2_t &p, int fast) {
@@ -1087,26 +1217,150 @@ DEVN void miller_loop_acc(fp12_t &f, const g2aff_t &Q, const g1aff_t &Pa) {
         }
     }
 }
+/* ---- homogeneous-projective Miller steps (executable spec
+ * in tests/test_miller_formulas.py).  T = (X, Y, Z) with x = X/Z, y = Y/Z on
+ * y^2 = x^3 + b', b' = 4 xi.  The doubling shares every square between the
+ * line and the point (3 mul + 6 sqr + 2 mul_fp against the Jacobian step's
+ * recomputation through g2_dbl); lines land in the same (c0, c3, c5) slots,
+ * scaled by an Fp2 factor that the final exponentiation removes. */
+DEVN void ml_dbl_step_h(g2_t &T, const g1aff_t &Pa, fp2_t &c0, fp2_t &c3, fp2_t &c5) {
+    fp2_t A, B, C, E, F, G, H, XX, t, t2;
+    fp2_mul(A, T.x, T.y);
+    fp2_half(A, A);                      /* XY/2 */
+    fp2_sqr(B, T.y);
+    fp2_sqr(C, T.z);
+    fp2_mul_xi(E, C);
+    fp2_dbl(E, E); fp2_dbl(E, E);        /* b' Z^2 */
+    fp2_dbl(t, E); fp2_add(E, E, t);     /* E = 3b' Z^2 */
+    fp2_dbl(t, E); fp2_add(F, E, t);     /* F = 3E */
+    fp2_add(G, B, F);
+    fp2_half(G, G);
+    fp2_add(H, T.y, T.z);
+    fp2_sqr(H, H);
+    fp2_add(t, B, C);
+    fp2_sub(H, H, t);                    /* 2YZ */
+    fp2_sqr(XX, T.x);
+    fp2_mul_fp(t, H, Pa.y);
+    fp2_mul_xi(c0, t);                   /* xi yP 2YZ */
+    fp2_sub(c3, B, E);                   /* Y^2 - 3b' Z^2 */
+    fp2_dbl(t, XX); fp2_add(t, t, XX);
+    fp2_mul_fp(t, t, Pa.x);
+    fp2_neg(c5, t);                      /* -3X^2 xP */
+    fp2_sub(t, B, F);
+    fp2_mul(T.x, A, t);
+    fp2_sqr(t, G);
+    fp2_sqr(t2, E);
+    fp2_dbl(G, t2); fp2_add(t2, t2, G);
+    fp2_sub(T.y, t, t2);                 /* G^2 - 3E^2 */
+    fp2_mul(T.z, B, H);
+}
+/* mixed addition T += Q, Q affine; theta = Y - y2 Z, lambda = X - x2 Z */
+DEVN void ml_add_step_h(g2_t &T, const g2aff_t &Q, const g1aff_t &Pa,
+                        fp2_t &c0, fp2_t &c3, fp2_t &c5) {
+    fp2_t th, la, C, D, E, F, G, H, t, t2;
+    fp2_mul(t, Q.y, T.z);
+    fp2_sub(th, T.y, t);
+    fp2_mul(t, Q.x, T.z);
+    fp2_sub(la, T.x, t);
+    fp2_mul_fp(t, la, Pa.y);
+    fp2_mul_xi(c0, t);                   /* xi yP lambda */
+    fp2_mul(t, Q.x, th);
+    fp2_mul(t2, Q.y, la);
+    fp2_sub(c3, t, t2);                  /* x2 theta - y2 lambda */
+    fp2_mul_fp(t, th, Pa.x);
+    fp2_neg(c5, t);                      /* -theta xP */
+    fp2_sqr(C, th);
+    fp2_sqr(D, la);
+    fp2_mul(E, la, D);
+    fp2_mul(F, T.z, C);
+    fp2_mul(G, T.x, D);
+    fp2_add(H, E, F);
+    fp2_dbl(t, G);
+    fp2_sub(H, H, t);
+    fp2_mul(T.x, la, H);
+    fp2_sub(t, G, H);
+    fp2_mul(t, th, t);
+    fp2_mul(t2, E, T.y);
+    fp2_sub(T.y, t, t2);
+    fp2_mul(T.z, T.z, E);
+}
+/* f *= l1 * l2 for two lines a0 + (a3 v + a5 v^2) w, b0 + (b3 v + b5 v^2) w.
+ * Their product m = m0 + m1 w has m0 full and m1 = (0, x, y): 6 fp2-mul.
+ * Folding m into f takes f0*m0 (6), f1*m1 (5, Karatsuba on the 2-sparse
+ * operand) and (f0+f1)(m0+m1) (6): 23 fp2-mul and one pass over f, against
+ * 30 and two passes for two fp12_mul_line calls. */
+DEVN void fp12_mul_line2(fp12_t &f, const fp2_t &a0, const fp2_t &a3, const fp2_t &a5,
+                         const fp2_t &b0, const fp2_t &b3, const fp2_t &b5) {
+    fp6_t m0, t0, t1, fs, tt, vt1;
+    fp2_t p00, p33, p55, x, y, s, u, q1, q2, q3;
+    fp2_mul(p00, a0, b0);
+    fp2_mul(p33, a3, b3);
+    fp2_mul(p55, a5, b5);
+    fp2_add(s, a3, a5);
+    fp2_add(u, b3, b5);
+    fp2_mul(q1, s, u);
+    fp2_sub(q1, q1, p33);
+    fp2_sub(q1, q1, p55);
+    fp2_mul_xi(m0.c1, q1);               /* xi (a3 b5 + a5 b3) */
+    fp2_mul_xi(s, p33);
+    fp2_add(m0.c0, p00, s);              /* a0 b0 + xi a3 b3 */
+    fp2_mul_xi(m0.c2, p55);              /* xi a5 b5 */
+    fp2_add(s, a0, a3);
+    fp2_add(u, b0, b3);
+    fp2_mul(x, s, u);
+    fp2_sub(x, x, p00);
+    fp2_sub(x, x, p33);                  /* a0 b3 + a3 b0 */
+    fp2_add(s, a0, a5);
+    fp2_add(u, b0, b5);
+    fp2_mul(y, s, u);
+    fp2_sub(y, y, p00);
+    fp2_sub(y, y, p55);                  /* a0 b5 + a5 b0 */
+    fp6_mul(t0, f.c0, m0);
+    {
+        const fp2_t &g0 = f.c1.c0, &g1 = f.c1.c1, &g2 = f.c1.c2;
+        fp2_mul(q1, g1, x);
+        fp2_mul(q2, g2, y);
+        fp2_add(s, g1, g2);
+        fp2_add(u, x, y);
+        fp2_mul(q3, s, u);
+        fp2_sub(q3, q3, q1);
+        fp2_sub(q3, q3, q2);             /* g1 y + g2 x */
+        fp2_mul_xi(t1.c0, q3);
+        fp2_mul(s, g0, x);
+        fp2_mul_xi(u, q2);
+        fp2_add(t1.c1, s, u);
+        fp2_mul(s, g0, y);
+        fp2_add(t1.c2, s, q1);
+    }
+    fp6_add(fs, f.c0, f.c1);
+    fp2_add(m0.c1, m0.c1, x);            /* m0 + m1 */
+    fp2_add(m0.c2, m0.c2, y);
+    fp6_mul(tt, fs, m0);
+    fp6_sub(tt, tt, t0);
+    fp6_sub(tt, tt, t1);
+    fp6_mul_v(vt1, t1);
+    fp6_add(f.c0, t0, vt1);
+    f.c1 = tt;
+}
 /* fused two-pairing Miller loop: f = f_{|z|,Q1}(P1) * f_{|z|,Q2}(P2), one
- * shared squaring chain (the standard multi-pairing product trick) */
+ * shared squaring chain (the standard multi-pairing product trick), the
+ * two legs' lines folded into f together */
 DEVN void miller_loop2(fp12_t &f, const g2aff_t &Q1, const g1aff_t &P1,
                        const g2aff_t &Q2, const g1aff_t &P2) {
     g2_t T1, T2;
     g2_from_affine(T1, Q1);
     g2_from_affine(T2, Q2);
-    fp2_t c0, c3, c5;
+    fp2_t a0, a3, a5, b0, b3, b5;
     fp12_one(f);
     for (int bit = 62; bit >= 0; bit--) {
         fp12_sqr(f, f);
-        ml_dbl_step(T1, P1, c0, c3, c5);
-        fp12_mul_line(f, c0, c3, c5);
-        ml_dbl_step(T2, P2, c0, c3, c5);
-        fp12_mul_line(f, c0, c3, c5);
+        ml_dbl_step_h(T1, P1, a0, a3, a5);
+        ml_dbl_step_h(T2, P2, b0, b3, b5);
+        fp12_mul_line2(f, a0, a3, a5, b0, b3, b5);
         if ((BLS_U >> bit) & 1) {
-            ml_add_step(T1, Q1, P1, c0, c3, c5);
-            fp12_mul_line(f, c0, c3, c5);
-            ml_add_step(T2, Q2, P2, c0, c3, c5);
-            fp12_mul_line(f, c0, c3, c5);
+            ml_add_step_h(T1, Q1, P1, a0, a3, a5);
+            ml_add_step_h(T2, Q2, P2, b0, b3, b5);
+            fp12_mul_line2(f, a0, a3, a5, b0, b3, b5);
         }
     }
 }
@@ -1170,7 +1424,7 @@ DEVN void final_exp(fp12_t &r, const fp12_t &f_in) {
     fp12_mul(d, u1, u2);
     fp12_conj(u1, c);
     fp12_mul(d, d, u1);
-    fp12_sqr(t, f);
+    fp12_cyc_sqr(t, f);                  /* f is cyclotomic after the easy part */
     fp12_mul(t, t, f);
     fp12_mul(r, d, t);
 }
