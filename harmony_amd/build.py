@@ -11,6 +11,15 @@ DIR = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(DIR, "csrc", "hbls_dev.hip")
 OUT = os.path.join(DIR, "libhbls.so")
 
+
+def _src_mtime():
+    """newest mtime over csrc/*: hbls_dev.hip #includes the .inc files, so an
+    edit to any of them makes every library stale"""
+    d = os.path.dirname(SRC)
+    return max(os.path.getmtime(os.path.join(d, f)) for f in os.listdir(d)
+               if os.path.isfile(os.path.join(d, f)))
+
+
 CMD = [
     "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-w",
     "-shared", "-fPIC", SRC, "-o", OUT,
@@ -25,7 +34,7 @@ CMD_CS = CMD[:-1] + [OUT_CS, "-DHBLS_FP2_RS"]
 
 def build_cs(force=False):
     if not force and os.path.exists(OUT_CS) and \
-            os.path.getmtime(OUT_CS) > os.path.getmtime(SRC):
+            os.path.getmtime(OUT_CS) > _src_mtime():
         return OUT_CS
     print("+", " ".join(CMD_CS), flush=True)
     subprocess.check_call(CMD_CS)
@@ -34,7 +43,7 @@ def build_cs(force=False):
 
 def build_count(force=False):
     if not force and os.path.exists(OUT_COUNT) and \
-            os.path.getmtime(OUT_COUNT) > os.path.getmtime(SRC):
+            os.path.getmtime(OUT_COUNT) > _src_mtime():
         return OUT_COUNT
     print("+", " ".join(CMD_COUNT), flush=True)
     subprocess.check_call(CMD_COUNT)
@@ -43,7 +52,7 @@ def build_count(force=False):
 
 def build(force=False):
     if not force and os.path.exists(OUT) and \
-            os.path.getmtime(OUT) > os.path.getmtime(SRC):
+            os.path.getmtime(OUT) > _src_mtime():
         return OUT
     print("+", " ".join(CMD), flush=True)
     subprocess.check_call(CMD)

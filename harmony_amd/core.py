@@ -84,6 +84,14 @@ def _load():
         ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
     lib.hbls_stream_get.argtypes = [ctypes.c_void_p, ctypes.c_uint32,
                                     ctypes.c_char_p, ctypes.c_char_p]
+    lib.hbls_stream_set_verify_mode.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.hbls_batch_verify_votes_grouped.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+        ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_char_p,
+        ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_int32)]
+    lib.hbls_rlc_last_stats.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
+    lib.hbls_rlc_last_stats.restype = None
     lib.hbls_fpmul_bench_waves.restype = ctypes.c_double
     lib.hbls_fpmul_bench_waves.argtypes = [ctypes.c_int, ctypes.c_int]
     return lib
@@ -126,6 +134,19 @@ def set_coop_threshold(n: int):
     """batches <= n use the wave-cooperative (latency) kernels; larger use
     thread-per-item (throughput).  -1 restores the env/default value."""
     _lib.hbls_set_coop_threshold(n)
+
+
+def rlc_chunk_size() -> int:
+    """votes per refinement chunk of the batched (random-combination) path"""
+    return _lib.hbls_rlc_chunk_size()
+
+
+def rlc_last_stats():
+    """[groups pairing-checked, groups failed, chunks re-checked, votes sent
+    per-item] of the last batched call on this thread"""
+    out = (ctypes.c_uint32 * 4)()
+    _lib.hbls_rlc_last_stats(out)
+    return list(out)
 
 
 def pk_from_sk(sk32: bytes) -> bytes:
@@ -310,6 +331,25 @@ class Committee:
                                             batch, res), "batch_verify_votes")
         return list(res)
 
+    def batch_verify_votes_grouped(self, key_idx, group_idx, sigs: bytes,
+                                   msgs: bytes, mlen: int):
+        """batch_verify_votes for votes that share messages: vote j signs
+        msgs[group_idx[j]]; one pairing per group (random combination), same
+        per-vote codes.  An out-of-range group index gives HBLS_ERR_BADINPUT
+        for that vote."""
+        batch = len(key_idx)
+        if len(group_idx) != batch or len(sigs) != 96 * batch:
+            raise ValueError("key_idx/group_idx/sigs length mismatch")
+        if mlen <= 0 or len(msgs) % mlen:
+            raise ValueError("msgs must be n_groups * mlen bytes")
+        idx = (ctypes.c_uint32 * batch)(*key_idx)
+        grp = (ctypes.c_uint32 * batch)(*group_idx)
+        res = (ctypes.c_int32 * batch)()
+        _check(_lib.hbls_batch_verify_votes_grouped(
+            self._h, idx, grp, sigs, msgs, mlen, len(msgs) // mlen, batch, res),
+            "batch_verify_votes_grouped")
+        return list(res)
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):
@@ -341,6 +381,12 @@ class Stream:
         arr = (ctypes.c_uint32 * k)(*slots)
         _check(_lib.hbls_stream_set_rounds(self._h, arr, k, payloads_cat,
                                            payload_len), "stream_set_rounds")
+
+    def set_verify_mode(self, mode: int):
+        """0: one pairing per vote (default); 1: batched, one pairing per
+        round present in a tick.  Results are the same either way."""
+        _check(_lib.hbls_stream_set_verify_mode(self._h, mode),
+               "stream_set_verify_mode")
 
     def process(self, key_idx, round_idx, sigs_cat: bytes):
         batch = len(key_idx)

@@ -3992,6 +3992,7 @@ struct hbls_stream {
     int32_t *ck_res;
     uint32_t *ck_slots;
     int ck_pending;       /* rounds in the in-flight check (0 = none) */
+    int verify_mode;      /* 0 per-item (default), 1 random-combination batched */
 };
 
 __global__ void k_stream_reset(uint32_t *bitmap, g2_t *agg, const uint32_t *slots,
@@ -4102,6 +4103,8 @@ __global__ void k_stream_gather_check(const uint32_t *bitmap, int nwords, int bm
     }
 }
 
+#include "hbls_rlc.inc"
+
 extern "C" void hbls_stream_free(hbls_stream *s);
 
 extern "C" hbls_stream *hbls_stream_create(const hbls_committee_t *c, int max_rounds) {
@@ -4142,6 +4145,7 @@ extern "C" hbls_stream *hbls_stream_create(const hbls_committee_t *c, int max_ro
         return nullptr;
     }
     s->ck_pending = 0;
+    s->verify_mode = 0;
     if (hipDeviceSynchronize() != hipSuccess) { hbls_stream_free(s); return nullptr; }
     return s;
 }
@@ -4206,7 +4210,9 @@ extern "C" int hbls_stream_process(hbls_stream *s, const uint32_t *key_idx,
                                    size_t batch, int32_t *results) {
     int rc = require_gpu();
     if (rc != HBLS_OK) return rc;
+    rlc_stats_reset();
     if (batch == 0 || n_active <= 0) return HBLS_ERR_BADINPUT;
+    if (s->verify_mode == 1 && batch > RLC_MAX_ITEMS) return HBLS_ERR_BADINPUT;
     for (int i = 0; i < n_active; i++)
         if (active_slots[i] >= (uint32_t)s->max_rounds) return HBLS_ERR_BADINPUT;
     DevBuf didx(batch * 4), dridx(batch * 4), dsig(batch * 96);
@@ -4227,7 +4233,21 @@ extern "C" int hbls_stream_process(hbls_stream *s, const uint32_t *key_idx,
     hipLaunchKernelGGL(k_stream_clamp, dim3(nb), dim3(64), 0, 0,
                        dridx.as<uint32_t>(), s->max_rounds,
                        dclamp.as<uint32_t>(), dpok.as<int32_t>(), (int)batch);
-    if ((int)batch <= coop_threshold()) {
+    if (s->verify_mode == 1) {
+        /* batched: one pairing per round slot present in the tick, grouped
+         * by the clamped round index (never by active_slots) */
+        if ((int)batch <= coop_threshold()) {
+            LAUNCH_COOP(k_g2_decompress_coop, batch, dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
+        } else {
+            hipLaunchKernelGGL(k_g2_decompress, dim3(nb), dim3(64), 0, 0,
+                               dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
+        }
+        rc = rlc_verify_chain(s->c, s->d_hm, s->d_hm_ok, (size_t)s->max_rounds, round_idx,
+                              didx.as<uint32_t>(), dclamp.as<uint32_t>(), dpok.as<int32_t>(),
+                              dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), dres.as<int32_t>(),
+                              batch);
+        if (rc != HBLS_OK) { tm.stop_and_store(); return rc; }
+    } else if ((int)batch <= coop_threshold()) {
         int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
         LAUNCH_COOP(k_g2_decompress_coop, batch, dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
         LAUNCH_COOP(k_verify_votes_coop, batch, s->c->d_table, (int)s->c->n, didx.as<uint32_t>(),

@@ -20,14 +20,19 @@ class StreamVerifier:
     """Single-round stream (window-checked).  External API kept from round 1:
     process_batch / final_check / accepted / rejected / bitmap / agg_sig."""
 
-    def __init__(self, pks_cat: bytes, n: int, payload: bytes, window: int = 100):
+    def __init__(self, pks_cat: bytes, n: int, payload: bytes, window: int = 100,
+                 batched: bool = False):
         """pks_cat: committee table; payload: the commit payload all votes of
-        this round sign (leader.go:250); window: aggregate-check period."""
+        this round sign (leader.go:250); window: aggregate-check period;
+        batched: verify each tick by random combination (one pairing per
+        round) instead of one pairing per vote — same results."""
         self.committee = core.Committee(pks_cat, n)
         self.n = n
         self.payload = payload
         self.window = window
         self.stream = core.Stream(self.committee, 1)
+        if batched:
+            self.stream.set_verify_mode(1)
         self.stream.set_rounds([0], payload, len(payload))
         self.accepted = 0
         self.rejected = 0
@@ -115,7 +120,8 @@ class MultiStreamVerifier:
     amortized across rounds in flight, so throughput tracks the batch rate
     instead of the single-pairing latency."""
 
-    def __init__(self, pks_cat: bytes, n: int, payloads, window: int = 100):
+    def __init__(self, pks_cat: bytes, n: int, payloads, window: int = 100,
+                 batched: bool = False):
         if len(set(len(p) for p in payloads)) > 1:
             raise ValueError("payloads must share a length for the batched launch")
         self.committee = core.Committee(pks_cat, n)
@@ -123,6 +129,8 @@ class MultiStreamVerifier:
         self.payloads = list(payloads)
         self.mlen = len(payloads[0])
         self.stream = core.Stream(self.committee, len(payloads))
+        if batched:
+            self.stream.set_verify_mode(1)
         self.stream.set_rounds(list(range(len(payloads))),
                                b"".join(payloads), self.mlen)
         self.rounds = [_RoundView(self, r) for r in range(len(payloads))]

@@ -118,6 +118,27 @@ int hbls_batch_verify_votes(const hbls_committee_t *c, const uint32_t *key_idx,
                             const uint8_t *sigs96, const uint8_t *msgs,
                             size_t msg_len, size_t batch, int32_t *results);
 
+/* same-message form of hbls_batch_verify_votes: vote j is checked on
+ * msgs[group_idx[j]] (msgs: n_groups * msg_len; hashes n_groups messages, not
+ * batch).  Votes of one group are verified by random linear combination —
+ * one pairing per group, e(sum r_i*pk_i, H) == e(G1, sum r_i*sig_i) with
+ * fresh secret 64-bit r_i from the OS CSPRNG (HBLS_ERR if that fails) — and a
+ * failing group is re-checked per chunk, then per vote, so results[j] carries
+ * exactly hbls_batch_verify_votes' codes; group_idx[j] >= n_groups gives that
+ * vote HBLS_ERR_BADINPUT.  A false accept has probability ~2^-64 per call
+ * (DESIGN.md "Random-combination batch verification"). */
+int hbls_batch_verify_votes_grouped(const hbls_committee_t *c, const uint32_t *key_idx,
+                                    const uint32_t *group_idx, const uint8_t *sigs96,
+                                    const uint8_t *msgs, size_t msg_len, size_t n_groups,
+                                    size_t batch, int32_t *results);
+/* votes per refinement chunk of the batched path */
+int hbls_rlc_chunk_size(void);
+/* counters of the last batched call on this thread (zeroed by every
+ * hbls_stream_process): out[0] groups pairing-checked, out[1] groups that
+ * failed, out[2] chunks pairing-checked in refinement, out[3] votes sent to
+ * the per-item kernel */
+void hbls_rlc_last_stats(uint32_t out[4]);
+
 /* batch hash-to-G2 (toG / mcl mapToG2 legacy) */
 int hbls_batch_hash_to_g2(const uint8_t *msgs, size_t msg_len, size_t batch,
                           uint8_t *out96s);
@@ -191,6 +212,12 @@ int hbls_stream_process(hbls_stream_t *s, const uint32_t *key_idx,
                         const uint32_t *round_idx, const uint8_t *sigs96,
                         const uint32_t *active_slots, int n_active,
                         size_t batch, int32_t *results);
+/* how hbls_stream_process verifies a tick: 0 = one pairing per vote (default),
+ * 1 = batched, one pairing per round slot present in the tick (see
+ * hbls_batch_verify_votes_grouped; votes group by their round index).
+ * Per-vote results, bitmaps and aggregates are the same in both modes.
+ * Other values return HBLS_ERR_BADINPUT. */
+int hbls_stream_set_verify_mode(hbls_stream_t *s, int mode);
 /* pairing-check rounds' resident aggregates vs their masks
  * (validator.go:224-228); ok[i] = 1/0 */
 int hbls_stream_check(hbls_stream_t *s, const uint32_t *slots, int k, int32_t *ok);

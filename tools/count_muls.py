@@ -2,7 +2,7 @@
 libhbls_count.so, -DHBLS_COUNT_MULS): settles the roofline denominator
 against the oracle's op-counter and locates algorithmic-work levers.
 
-Run on a GPU box:  python tools/count_muls.py
+Run on a GPU box:  python tools/count_muls.py [OUT.json]
 """
 import ctypes
 import json
@@ -69,6 +69,46 @@ for thr, name in ((0, "scalar"), (1 << 30, "coop")):
         lambda: lib.hbls_agg_verify(com, bm, sig, msg, len(msg)))
 lib.hbls_set_coop_threshold(-1)
 
+# vote verification, fp-mul per vote: one all-valid single-group tick of 4096
+# through the stream, per-item pairing (mode 0) against random-combination
+# batching (mode 1).  Both figures include the signature decompress.
+lib.hbls_stream_create.restype = ctypes.c_void_p
+lib.hbls_stream_create.argtypes = [ctypes.c_void_p, ctypes.c_int]
+lib.hbls_stream_free.argtypes = [ctypes.c_void_p]
+lib.hbls_stream_set_rounds.argtypes = [
+    ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int,
+    ctypes.c_char_p, ctypes.c_size_t]
+lib.hbls_stream_set_verify_mode.argtypes = [ctypes.c_void_p, ctypes.c_int]
+lib.hbls_stream_process.argtypes = [
+    ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+    ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p,
+    ctypes.POINTER(ctypes.c_uint32), ctypes.c_int,
+    ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]
+vsigs = ctypes.create_string_buffer(96 * n)
+assert lib.hbls_batch_sign(sks, msg * n, ctypes.c_size_t(len(msg)),
+                           ctypes.c_size_t(n), vsigs) == 1
+kidx = (ctypes.c_uint32 * n)(*range(n))
+ridx = (ctypes.c_uint32 * n)()
+slot0 = (ctypes.c_uint32 * 1)(0)
+vres = (ctypes.c_int32 * n)()
+# thread-per-item kernels throughout: the wave-cooperative kernels carry
+# their own multiplier, which the counter does not see
+lib.hbls_set_coop_threshold(0)
+for mode, name in ((0, "item"), (1, "batched")):
+    st = lib.hbls_stream_create(com, 1)
+    assert st
+    assert lib.hbls_stream_set_rounds(st, slot0, 1, msg, len(msg)) == 1
+    assert lib.hbls_stream_set_verify_mode(st, mode) == 1
+    out[f"vote_verify_per_vote_{name}"] = count(
+        lambda: lib.hbls_stream_process(st, kidx, ridx, vsigs.raw, slot0, 1, n, vres)) // n
+    assert list(vres) == [1] * n, name
+    lib.hbls_stream_free(st)
+lib.hbls_set_coop_threshold(-1)
+stats =(ctypes.c_uint32 * 4)()
+lib.hbls_rlc_last_stats(stats)
+out["vote_verify_batched_rlc_stats"] = list(stats)
+assert out["vote_verify_per_vote_batched"] < out["vote_verify_per_vote_item"]
+
 # oracle comparison
 from oracle import capi
 capi.reset_op_count()
@@ -78,5 +118,7 @@ assert oc.agg_verify(bm, sig, msg) is True
 out["oracle_agg_verify_total"] = capi.op_count()
 
 print(json.dumps(out, indent=1))
-with open(os.path.join(REPO, "gpurun_out", "r2d_mulcounts.json"), "w") as f:
-    json.dump(out, f, indent=1)
+if len(sys.argv) > 1:      # optional: also keep the counts in a file
+    os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
+    with open(sys.argv[1], "w") as f:
+        json.dump(out, f, indent=1)
