@@ -92,6 +92,11 @@ def _load():
         ctypes.POINTER(ctypes.c_int32)]
     lib.hbls_rlc_last_stats.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
     lib.hbls_rlc_last_stats.restype = None
+    lib.hbls_set_agg_verify_mode.argtypes = [ctypes.c_int]
+    lib.hbls_set_aggrlc_threshold.argtypes = [ctypes.c_int]
+    lib.hbls_set_aggrlc_threshold.restype = None
+    lib.hbls_aggrlc_last_stats.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
+    lib.hbls_aggrlc_last_stats.restype = None
     lib.hbls_fpmul_bench_waves.restype = ctypes.c_double
     lib.hbls_fpmul_bench_waves.argtypes = [ctypes.c_int, ctypes.c_int]
     return lib
@@ -146,6 +151,32 @@ def rlc_last_stats():
     per-item] of the last batched call on this thread"""
     out = (ctypes.c_uint32 * 4)()
     _lib.hbls_rlc_last_stats(out)
+    return list(out)
+
+
+def set_agg_verify_mode(mode: int):
+    """pairing stage of batch_agg_verify / batch_seal_verify: 0 exact (one
+    final exponentiation per item), 1 combined (one per chunk of
+    aggrlc_chunk_size() items, from the threshold up), -1 auto (default)"""
+    _check(_lib.hbls_set_agg_verify_mode(mode), "set_agg_verify_mode")
+
+
+def set_aggrlc_threshold(n: int):
+    """smallest batch that takes the combined aggregate-verify path; -1
+    restores the default"""
+    _lib.hbls_set_aggrlc_threshold(n)
+
+
+def aggrlc_chunk_size() -> int:
+    """items that share one final exponentiation on the combined path"""
+    return _lib.hbls_aggrlc_chunk_size()
+
+
+def aggrlc_last_stats():
+    """[chunks checked, chunks failed, items re-checked per item] of the last
+    aggregate-verify call on this thread; zeros when it ran the exact path"""
+    out = (ctypes.c_uint32 * 3)()
+    _lib.hbls_aggrlc_last_stats(out)
     return list(out)
 
 

@@ -2333,6 +2333,10 @@ static thread_local uint64_t g_last_ns = 0;
 static thread_local uint64_t g_stage_ns[8] = {0};
 static std::once_flag g_init_flag;
 static int g_init_rc = HBLS_ERR_NOGPU;
+/* combined aggregate verify (hbls_aggrlc.inc, included below) */
+static int aggrlc_init_tables(void);
+static bool aggrlc_wanted(size_t batch);
+static void aggrlc_stats_reset(void);
 
 #define HIP_OK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
     fprintf(stderr, "hbls: %s failed: %s\n", #expr, hipGetErrorString(_e)); return HBLS_ERR; } } while (0)
@@ -2360,6 +2364,9 @@ extern "C" int hbls_init(int device) {
     if (hipMalloc(&p, 64) != hipSuccess) return HBLS_ERR;
     hipFree(p);
     g_init_rc = HBLS_OK;
+    /* fixed-base table of -G1 for the combined aggregate verify; without it
+     * every call takes the exact path */
+    (void)aggrlc_init_tables();
     return HBLS_OK;
 }
 
@@ -2667,6 +2674,11 @@ extern "C" int hbls_mask_aggregate_g1(const hbls_committee_t *c, const uint8_t *
     return HBLS_OK;
 }
 
+static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_saff,
+                         const int32_t *d_sflags, const int32_t *d_hok,
+                         int32_t *d_res, size_t batch);
+#define AGGRLC_FALLBACK 2       /* aggrlc_verify wrote nothing: run the exact path */
+
 /* the four-stage aggregate-verify pipeline over DEVICE-resident inputs
  * (bitmaps, serialized sigs, messages) — shared by the host-buffer entry
  * points and the HBM-direct seal-blob path. */
@@ -2679,6 +2691,7 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
     if (dagg.err || dhm.err || dsaff.err || dsflags.err || dhok.err || dres.err)
         return HBLS_ERR;
     int nb = (int)((batch + 63) / 64);
+    aggrlc_stats_reset();
     hipEvent_t ev[5];
     for (int i = 0; i < 5; i++) (void)hipEventCreate(&ev[i]);
     (void)hipEventRecord(ev[0], 0);
@@ -2704,7 +2717,15 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
                            d_sig, dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
     }
     (void)hipEventRecord(ev[3], 0);
-    if ((int)batch <= coop_threshold()) {
+    int arc = AGGRLC_FALLBACK;
+    if (aggrlc_wanted(batch)) {
+        arc = aggrlc_verify(dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
+                            dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), batch);
+        if (arc != HBLS_OK && arc != AGGRLC_FALLBACK) return arc;
+    }
+    if (arc == HBLS_OK) {
+        /* combined path wrote every result */
+    } else if ((int)batch <= coop_threshold()) {
         int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
         LAUNCH_COOP(k_verify_coop, batch, dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
                            dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), (int)batch);
@@ -4104,6 +4125,7 @@ __global__ void k_stream_gather_check(const uint32_t *bitmap, int nwords, int bm
 }
 
 #include "hbls_rlc.inc"
+#include "hbls_aggrlc.inc"
 
 extern "C" void hbls_stream_free(hbls_stream *s);
 

@@ -232,6 +232,28 @@ int hbls_stream_check_poll(hbls_stream_t *s, int32_t *ok);
 int hbls_stream_get(hbls_stream_t *s, uint32_t slot, uint8_t *bitmap_out,
                     uint8_t agg96_out[96]);
 
+/* ---- combined aggregate verify ----
+ * How hbls_batch_agg_verify / hbls_batch_seal_verify run their pairing stage:
+ *   0  exact: one final exponentiation per item
+ *   1  combined: items are weighted by fresh secret 64-bit scalars and share
+ *      one final exponentiation per chunk of hbls_aggrlc_chunk_size() items,
+ *      for batches >= the threshold; the items of a failing chunk are
+ *      re-checked exactly, so per-item results equal mode 0 except that an
+ *      invalid item is accepted with probability ~2^-64 per chunk
+ *  -1  auto (default): combined for batches >= the threshold that are also
+ *      above the cooperative-kernel threshold, exact otherwise
+ * Other values return HBLS_ERR_BADINPUT.  The environment variable
+ * HBLS_AGG_VERIFY_MODE (0/1) sets the initial mode.  When the OS random
+ * source or the combination's device memory is unavailable the call takes
+ * the exact path.  hbls_batch_agg_verify_partials always runs mode 0 (its
+ * external partial sums are not subgroup-checked). */
+int hbls_set_agg_verify_mode(int mode);
+void hbls_set_aggrlc_threshold(int min_batch);   /* < 0 restores the default */
+int hbls_aggrlc_chunk_size(void);
+/* chunks checked, chunks failed, items re-checked per item — of the last
+ * aggregate-verify call on this thread (zeros when it ran exact) */
+void hbls_aggrlc_last_stats(uint32_t out[3]);
+
 /* batch Keccak-256 (consensus message digests, crypto/hash/hash.go:9-15) */
 int hbls_batch_keccak256(const uint8_t *msgs, size_t msg_len, size_t batch,
                          uint8_t *out32s);

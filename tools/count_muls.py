@@ -69,6 +69,33 @@ for thr, name in ((0, "scalar"), (1 << 30, "coop")):
         lambda: lib.hbls_agg_verify(com, bm, sig, msg, len(msg)))
 lib.hbls_set_coop_threshold(-1)
 
+# aggregate verify, fp-mul per item: one all-valid batch of 64 (one chunk)
+# through the thread-per-item kernels, exact (mode 0, a final exponentiation
+# per item) against combined (mode 1, one per chunk).  Both
+# figures are whole-pipeline; their difference is the verify stage's saving.
+lib.hbls_batch_agg_verify.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p,
+                                      ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t,
+                                      ctypes.POINTER(ctypes.c_int32)]
+nb = 64
+bres = (ctypes.c_int32 * nb)()
+lib.hbls_set_coop_threshold(0)
+lib.hbls_set_aggrlc_threshold(1)
+for mode, name in ((0, "exact"), (1, "combined")):
+    assert lib.hbls_set_agg_verify_mode(mode) == 1
+    out[f"agg_verify_per_item_{name}"] = count(
+        lambda: lib.hbls_batch_agg_verify(com, bm * nb, sig * nb, msg * nb, len(msg),
+                                          nb, bres)) // nb
+    assert list(bres) == [1] * nb, name
+astats = (ctypes.c_uint32 * 3)()
+lib.hbls_aggrlc_last_stats(astats)
+out["agg_verify_combined_stats"] = list(astats)
+assert list(astats) == [1, 0, 0]
+out["verify_stage_saving_per_item"] = (out["agg_verify_per_item_exact"] -
+                                       out["agg_verify_per_item_combined"])
+lib.hbls_set_agg_verify_mode(-1)
+lib.hbls_set_aggrlc_threshold(-1)
+lib.hbls_set_coop_threshold(-1)
+
 # vote verification, fp-mul per vote: one all-valid single-group tick of 4096
 # through the stream, per-item pairing (mode 0) against random-combination
 # batching (mode 1).  Both figures include the signature decompress.
