@@ -15,6 +15,9 @@ HBLS_FALSE = 0
 HBLS_ERR = -1
 HBLS_ERR_NOGPU = -2
 HBLS_ERR_BADINPUT = -3
+HBLS_NOQUORUM = -4
+NOQUORUM = HBLS_NOQUORUM                 # per-item result of the *_quorum entries
+TWO_THIRDS_DEC = 666666666666666667      # numeric.NewDec(2).Quo(numeric.NewDec(3)), 1e-18 units
 
 
 class HblsError(RuntimeError):
@@ -23,6 +26,10 @@ class HblsError(RuntimeError):
 
 class NoGpuError(HblsError):
     pass
+
+
+class BadInputError(HblsError, ValueError):
+    """HBLS_ERR_BADINPUT; a ValueError, as it has always been raised"""
 
 
 def _load():
@@ -97,6 +104,19 @@ def _load():
     lib.hbls_set_aggrlc_threshold.restype = None
     lib.hbls_aggrlc_last_stats.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
     lib.hbls_aggrlc_last_stats.restype = None
+    u64p, u32p, i32p = (ctypes.POINTER(t) for t in
+                        (ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32))
+    lib.hbls_committee_set_quorum.argtypes = [ctypes.c_void_p, u64p, ctypes.c_uint64]
+    lib.hbls_mask_power.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t,
+                                    u64p, u32p]
+    lib.hbls_agg_verify_quorum.argtypes = lib.hbls_agg_verify.argtypes
+    lib.hbls_batch_agg_verify_quorum.argtypes = lib.hbls_batch_agg_verify.argtypes
+    lib.hbls_batch_seal_verify_quorum.argtypes = lib.hbls_batch_seal_verify.argtypes
+    lib.hbls_stream_power.argtypes = [ctypes.c_void_p, u32p, ctypes.c_int,
+                                      u64p, u32p, i32p]
+    lib.hbls_last_stage_ns.argtypes = [ctypes.c_int]
+    lib.hbls_copy_bench_ns.restype = ctypes.c_uint64
+    lib.hbls_copy_bench_ns.argtypes = [ctypes.c_size_t]
     lib.hbls_fpmul_bench_waves.restype = ctypes.c_double
     lib.hbls_fpmul_bench_waves.argtypes = [ctypes.c_int, ctypes.c_int]
     return lib
@@ -109,7 +129,7 @@ def _check(rc, what):
     if rc == HBLS_ERR_NOGPU:
         raise NoGpuError(f"{what}: no AMD GPU available (product path requires gfx950)")
     if rc == HBLS_ERR_BADINPUT:
-        raise ValueError(f"{what}: bad input")
+        raise BadInputError(f"{what}: bad input")
     if rc < 0:
         raise HblsError(f"{what}: error {rc}")
     return rc
@@ -129,6 +149,13 @@ def init(device=-1):
 
 def last_kernel_ns() -> int:
     return _lib.hbls_last_kernel_ns()
+
+
+def last_stage_ns(i: int) -> int:
+    """device time of stage i of the last aggregate-verify call on this
+    thread: 0 mask aggregate, 1 hash-to-G2, 2 decompress, 3 pairing,
+    7 quorum by mask (k_mask_power)"""
+    return _lib.hbls_last_stage_ns(i)
 
 
 def set_g2_cofactor_mode(fast: bool):
@@ -291,6 +318,7 @@ class Committee:
                 raise NoGpuError("committee_build: no AMD GPU")
             raise ValueError("committee_build: invalid pubkey in table")
         self.n = n
+        self._quorum_set = False
 
     def _bitmap_len(self) -> int:
         return (self.n + 7) >> 3
@@ -344,6 +372,60 @@ class Committee:
         _check(_lib.hbls_batch_seal_verify(self._h, sig_bitmaps, blob_len,
                                            msgs, mlen, batch, res),
                "batch_seal_verify")
+        return list(res)
+
+    # -- quorum by mask
+    def set_quorum(self, power=None, threshold=None):
+        """the epoch's qrVerifier (engine.go:644-659).  power None: uniform
+        policy, quorum is popcount > floor(2n/3).  Otherwise n voting powers
+        in 1e-18 units (votepower.compute) and quorum is masked sum >
+        threshold (default TWO_THIRDS_DEC).  Call before sharing the
+        committee between threads."""
+        if power is None:
+            rc = _lib.hbls_committee_set_quorum(self._h, None, 0)
+        else:
+            if len(power) != self.n:
+                raise ValueError(f"set_quorum: expected {self.n} powers got {len(power)}")
+            if any(p < 0 or p >> 64 for p in power):
+                raise BadInputError("set_quorum: power out of range")
+            arr = (ctypes.c_uint64 * self.n)(*power)
+            rc = _lib.hbls_committee_set_quorum(
+                self._h, arr, TWO_THIRDS_DEC if threshold is None else threshold)
+        _check(rc, "set_quorum")
+        self._quorum_set = True
+
+    def mask_power(self, bitmaps: bytes, batch: int):
+        """(powers, counts): masked voting-power sum and in-range popcount
+        of each bitmap (ComputeTotalPowerByMask / CountOneBits)"""
+        self._check_bitmaps(bitmaps, batch, "mask_power")
+        pw = (ctypes.c_uint64 * batch)()
+        cn = (ctypes.c_uint32 * batch)()
+        _check(_lib.hbls_mask_power(self._h, bitmaps, batch, pw, cn), "mask_power")
+        return list(pw), list(cn)
+
+    def agg_verify_quorum(self, bitmap: bytes, sig96: bytes, msg: bytes) -> int:
+        """verifySignature (engine.go:619-642): 1 accept, 0 reject, NOQUORUM;
+        other negative codes raise"""
+        self._check_bitmaps(bitmap, 1, "agg_verify_quorum")
+        rc = _lib.hbls_agg_verify_quorum(self._h, bitmap, sig96, msg, len(msg))
+        return rc if rc == NOQUORUM else _check(rc, "agg_verify_quorum")
+
+    def batch_agg_verify_quorum(self, bitmaps: bytes, sigs: bytes, msgs: bytes,
+                                mlen: int, batch: int):
+        """batch_agg_verify behind the quorum-by-mask gate: items without
+        quorum get NOQUORUM and never reach the pairing"""
+        self._check_bitmaps(bitmaps, batch, "batch_agg_verify_quorum")
+        res = (ctypes.c_int32 * batch)()
+        _check(_lib.hbls_batch_agg_verify_quorum(self._h, bitmaps, sigs, msgs, mlen,
+                                                 batch, res), "batch_agg_verify_quorum")
+        return list(res)
+
+    def batch_seal_verify_quorum(self, sig_bitmaps: bytes, blob_len: int,
+                                 msgs: bytes, mlen: int, batch: int):
+        res = (ctypes.c_int32 * batch)()
+        _check(_lib.hbls_batch_seal_verify_quorum(self._h, sig_bitmaps, blob_len,
+                                                  msgs, mlen, batch, res),
+               "batch_seal_verify_quorum")
         return list(res)
 
     def msm(self, scalars_cat: bytes) -> bytes:
@@ -456,6 +538,18 @@ class Stream:
         k = _check(_lib.hbls_stream_check_poll(self._h, ok), "stream_check_poll")
         self._pending_check = None
         return {s: bool(ok[i] == 1) for i, s in enumerate(slots[:k])}
+
+    def power(self, slots):
+        """(power, count, quorum) lists for the given round slots, tallied
+        on the device from the resident bitmaps (IsQuorumAchieved).  quorum
+        is None until the committee's set_quorum has been called."""
+        k = len(slots)
+        arr = (ctypes.c_uint32 * k)(*slots)
+        pw = (ctypes.c_uint64 * k)()
+        cn = (ctypes.c_uint32 * k)()
+        qr = (ctypes.c_int32 * k)() if self.committee._quorum_set else None
+        _check(_lib.hbls_stream_power(self._h, arr, k, pw, cn, qr), "stream_power")
+        return list(pw), list(cn), (list(qr) if qr is not None else None)
 
     def get(self, slot: int):
         """returns (bitmap bytes, serialized aggregate sig 96B)"""

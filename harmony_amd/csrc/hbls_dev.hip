@@ -2575,6 +2575,12 @@ struct hbls_committee {
     g1aff_t *d_wtab;    /* 8-bit window table (n >= 16384): groups x 255 */
     uint8_t *d_winf;    /* per-entry infinity flags for d_wtab */
     size_t n;
+    /* quorum by mask (hbls_quorum.inc): voting power per key in 1e-18 units,
+     * quorum <=> masked sum > q_threshold */
+    uint64_t *d_power;
+    uint64_t q_threshold;
+    int q_uniform;      /* all weights 1: popcount path */
+    int q_set;          /* hbls_committee_set_quorum was called */
 };
 extern "C" hbls_committee_t *hbls_committee_build(const uint8_t *pks48, size_t n) {
     if (require_gpu() != HBLS_OK) return nullptr;
@@ -2597,6 +2603,21 @@ extern "C" hbls_committee_t *hbls_committee_build(const uint8_t *pks48, size_t n
     c->d_full_sum = nullptr;
     c->d_wtab = nullptr;
     c->d_winf = nullptr;
+    /* uniform voting power until hbls_committee_set_quorum says otherwise */
+    c->d_power = nullptr;
+    c->q_threshold = (uint64_t)(2 * n / 3);
+    c->q_uniform = 1;
+    c->q_set = 0;
+    {
+        std::vector<uint64_t> ones(n, 1);
+        if (hipMalloc(&c->d_power, n ? n * 8 : 8) != hipSuccess ||
+            hipMemcpy(c->d_power, ones.data(), n * 8, hipMemcpyHostToDevice) != hipSuccess) {
+            if (c->d_power) hipFree(c->d_power);
+            hipFree(d_table);
+            delete c;
+            return nullptr;
+        }
+    }
     /* 8-bit window table: 255 subset sums per 8-key group (n x 3060 B:
      * ~12.5 MB at n=4096, ~200 MB at n=65536; skipped silently if the
      * transient allocations fail) */
@@ -2649,6 +2670,7 @@ extern "C" void hbls_committee_free(hbls_committee_t *c) {
         if (c->d_full_sum) hipFree(c->d_full_sum);
         if (c->d_wtab) hipFree(c->d_wtab);
         if (c->d_winf) hipFree(c->d_winf);
+        if (c->d_power) hipFree(c->d_power);
         delete c;
     }
 }
@@ -4126,6 +4148,7 @@ __global__ void k_stream_gather_check(const uint32_t *bitmap, int nwords, int bm
 
 #include "hbls_rlc.inc"
 #include "hbls_aggrlc.inc"
+#include "hbls_quorum.inc"
 
 extern "C" void hbls_stream_free(hbls_stream *s);
 

@@ -61,9 +61,13 @@ class Decider:
     stake-weighted (one-node-staked-vote.go, >2/3 stake) policies.
 
     members: list[PublicKeyWrapper]; stakes: optional list of int/Fraction
-    (None -> uniform voting, mirroring SuperMajorityVote)."""
+    (None -> uniform voting, mirroring SuperMajorityVote).
 
-    def __init__(self, members, stakes=None):
+    power_units: optional voting power per member as numeric.Dec integers
+    (votepower.compute's list) — the exact weights batch_verify_seals_quorum
+    enforces on the device; without it that entry applies the uniform policy."""
+
+    def __init__(self, members, stakes=None, power_units=None):
         self.members = list(members)
         self.index = {w.Bytes: i for i, w in enumerate(self.members)}
         self.ballots = BallotBox()
@@ -71,7 +75,11 @@ class Decider:
         if stakes is not None:
             total = sum(Fraction(s) for s in stakes)
             self.stakes = [Fraction(s) / total for s in stakes]
+        if power_units is not None and len(power_units) != len(self.members):
+            raise ValueError("power_units must hold one value per member")
+        self.power_units = None if power_units is None else list(power_units)
         self._committee_cache = None   # built lazily: host-only logic needs no GPU
+        self._quorum_set = False
 
     @property
     def _committee(self):
@@ -152,3 +160,15 @@ class Decider:
                            mlen: int, batch: int):
         """sync-path batch seal verification (stagedstreamsync/sig_verify.go)"""
         return self._committee.batch_agg_verify(bitmaps, sigs, payloads, mlen, batch)
+
+    def batch_verify_seals_quorum(self, bitmaps: bytes, sigs: bytes, payloads: bytes,
+                                  mlen: int, batch: int):
+        """verifySignature (engine.go:619-642) for a batch, quorum included:
+        IsQuorumAchievedByMask runs on the device ahead of the pairing, in
+        numeric.Dec's integer arithmetic (power_units against twoThird, or the
+        uniform 2f+1 count).  Per item: 1 / 0 / core.NOQUORUM / other
+        negative codes."""
+        if not self._quorum_set:
+            self._committee.set_quorum(self.power_units)
+            self._quorum_set = True
+        return self._committee.batch_agg_verify_quorum(bitmaps, sigs, payloads, mlen, batch)

@@ -35,7 +35,12 @@ enum {
     HBLS_ERR = -1,
     HBLS_ERR_NOGPU = -2,
     HBLS_ERR_BADINPUT = -3,
+    HBLS_NOQUORUM = -4,     /* per-item result of the _quorum entries only */
 };
+
+/* numeric.NewDec(2).Quo(numeric.NewDec(3)) as the integer inside the Dec
+ * (twoThird, one-node-staked-vote.go:23; Precision = 18, half-to-even) */
+#define HBLS_TWO_THIRDS_DEC 666666666666666667ULL
 
 /* blsInit(BLS12_381) (bls.h) — called once per process (crypto/bls/mask.go:18-20).
  * Initializes the HIP device context; device = HIP device index (normally
@@ -188,6 +193,55 @@ int hbls_batch_seal_verify(const hbls_committee_t *c,
                            const uint8_t *msgs, size_t msg_len,
                            size_t batch, int32_t *results);
 
+/* ---- quorum by mask ----
+ * Voting power crosses the ABI as uint64_t in units of 1e-18 — the integer
+ * inside a numeric.Dec (Precision = 18, numeric/decimal.go:22); a committee's
+ * powers sum to 1e18 < 2^60, so every masked sum is exact.  One rule covers
+ * both policies: quorum <=> masked sum > threshold, strictly.  Only bits
+ * i < n count (Mask.SetMask, crypto/bls/mask.go:121-132); padding bits of the
+ * last byte are ignored.
+ *
+ * qrVerifier of an epoch context (internal/chain/engine.go:644-659,
+ * quorum.go SetVoters).
+ * power == NULL: uniform policy (one-node-one-vote.go:57-72), threshold
+ * ignored and set to floor(2n/3) — popcount > floor(2n/3) is the reference's
+ * popcount >= n*2/3 + 1.
+ * power != NULL: n values (OverallPercent, one-node-staked-vote.go:151-164),
+ * normally with threshold HBLS_TWO_THIRDS_DEC; HBLS_ERR_BADINPUT if the n
+ * values sum above 2^63.
+ * Call before the committee is shared between threads. */
+int hbls_committee_set_quorum(hbls_committee_t *c, const uint64_t *power,
+                              uint64_t threshold);
+
+/* ComputeTotalPowerByMask (one-node-staked-vote.go:166-188) / CountOneBits
+ * (one-node-one-vote.go:62), batch form; bitmaps: batch * ceil(n/8) bytes; either output
+ * may be NULL.  Before hbls_committee_set_quorum every weight is 1, so power
+ * equals count. */
+int hbls_mask_power(const hbls_committee_t *c, const uint8_t *bitmaps, size_t batch,
+                    uint64_t *power_out, uint32_t *count_out);
+
+/* verifySignature (internal/chain/engine.go:619-642) complete:
+ * IsQuorumAchievedByMask, then the pairing.  Arguments and per-item codes as
+ * in hbls_batch_agg_verify / hbls_batch_seal_verify / hbls_agg_verify, plus
+ * HBLS_NOQUORUM ("not enough signature collected") for an item whose mask
+ * has no quorum.  Such an item is dropped on the device before hash-to-G2,
+ * decompression and pairing, so it cannot fail a chunk of the combined mode.
+ * One ordering difference to the reference: a quorumless item reports
+ * HBLS_NOQUORUM even when its signature does not deserialise, where the
+ * reference reports the deserialisation error first (DecodeSigBitmap runs
+ * before the quorum check); both are errors there.
+ * HBLS_ERR_BADINPUT until hbls_committee_set_quorum has been called: a
+ * policy is never assumed. */
+int hbls_batch_agg_verify_quorum(const hbls_committee_t *c, const uint8_t *bitmaps,
+                                 const uint8_t *sigs96, const uint8_t *msgs,
+                                 size_t msg_len, size_t batch, int32_t *results);
+int hbls_batch_seal_verify_quorum(const hbls_committee_t *c,
+                                  const uint8_t *sig_bitmaps, size_t blob_len,
+                                  const uint8_t *msgs, size_t msg_len,
+                                  size_t batch, int32_t *results);
+int hbls_agg_verify_quorum(const hbls_committee_t *c, const uint8_t *bitmap,
+                           const uint8_t sig96[96], const uint8_t *msg, size_t msg_len);
+
 /* AggregateSig batch form (crypto/bls/mask.go:57-64): out = sum of n sigs */
 int hbls_g2_aggregate(const uint8_t *sigs96, size_t n, uint8_t out96[96]);
 
@@ -231,6 +285,16 @@ int hbls_stream_check_poll(hbls_stream_t *s, int32_t *ok);
  * (consensus_service.go:305-322 commitSigAndBitmap shape) */
 int hbls_stream_get(hbls_stream_t *s, uint32_t slot, uint8_t *bitmap_out,
                     uint8_t agg96_out[96]);
+
+/* IsQuorumAchieved / the tally of resident rounds (quorum.go:409,
+ * consensus/leader.go:240,319): masked power, in-range popcount and the
+ * quorum verdict (1/0) of each listed round come back — 16 B per round
+ * instead of the bitmap.  Any output may be NULL.  power_out and count_out
+ * work before hbls_committee_set_quorum (uniform weights); quorum_out needs
+ * it (HBLS_ERR_BADINPUT otherwise).  A slot >= max_rounds fails the call
+ * with HBLS_ERR_BADINPUT, as in hbls_stream_get. */
+int hbls_stream_power(hbls_stream_t *s, const uint32_t *slots, int k,
+                      uint64_t *power_out, uint32_t *count_out, int32_t *quorum_out);
 
 /* ---- combined aggregate verify ----
  * How hbls_batch_agg_verify / hbls_batch_seal_verify run their pairing stage:
