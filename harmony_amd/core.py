@@ -97,6 +97,19 @@ def _load():
         ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_char_p,
         ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_int32)]
+    lib.hbls_vote_key_sums.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+        ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.c_char_p,
+        ctypes.POINTER(ctypes.c_int32)]
+    lib.hbls_batch_verify_votes_multi.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+        ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_char_p,
+        ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]
+    lib.hbls_stream_process_multi.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+        ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+        ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int,
+        ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]
     lib.hbls_rlc_last_stats.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
     lib.hbls_rlc_last_stats.restype = None
     lib.hbls_set_agg_verify_mode.argtypes = [ctypes.c_int]
@@ -308,6 +321,44 @@ def parse_commit_sig_bitmap(payload: bytes):
     return sig.raw, bm.raw[:n]
 
 
+def pack_key_lists(key_lists, batch=None):
+    """Signer sets in the CSR form of the multi-key entries:
+    returns (key_off, key_idx) with vote j signed by
+    key_idx[key_off[j]:key_off[j + 1]].  Lists are taken as they are — whether
+    one is well formed (non-empty, in range, strictly ascending) is the
+    device's per-vote verdict.  batch, when given, is the number of votes the
+    caller's other arrays hold; a different number of lists raises ValueError.
+    Needs no GPU."""
+    if batch is not None and len(key_lists) != batch:
+        raise ValueError(f"expected {batch} key lists got {len(key_lists)}")
+    key_off, key_idx = [0], []
+    for keys in key_lists:
+        for k in keys:
+            if not 0 <= k < 1 << 32:
+                raise ValueError(f"key index {k} is not a uint32")
+            key_idx.append(k)
+        key_off.append(len(key_idx))
+    if key_off[-1] >= 1 << 31:
+        raise ValueError("too many key indices for one call")
+    return key_off, key_idx
+
+
+def _csr_arrays(key_lists, batch, csr=None):
+    """ctypes (key_off, key_idx, batch) of key_lists, or of a caller's raw
+    csr=(key_off, key_idx) pair, which is passed on unchecked but for its
+    length"""
+    if csr is None:
+        key_off, key_idx = pack_key_lists(key_lists, batch)
+    else:
+        key_off, key_idx = csr
+        if not key_off or (batch is not None and len(key_off) != batch + 1):
+            raise ValueError("key_off must hold batch + 1 entries")
+        if any(o > len(key_idx) for o in key_off):
+            raise ValueError("key_off points past key_idx")
+    return ((ctypes.c_uint32 * len(key_off))(*key_off),
+            (ctypes.c_uint32 * max(len(key_idx), 1))(*key_idx), len(key_off) - 1)
+
+
 class Committee:
     """Device-resident, validated pubkey table (UpdateParticipants equivalent)."""
 
@@ -463,6 +514,34 @@ class Committee:
             "batch_verify_votes_grouped")
         return list(res)
 
+    # -- multi-key votes
+    def vote_key_sums(self, key_lists, csr=None):
+        """(sums, ok): the serialized key sum of each vote's signer set
+        (signerPubKey, leader.go:165-172) and 1 / HBLS_ERR_BADINPUT per vote.
+        An infinity sum and a malformed vote's block are 48 zero bytes."""
+        off, idx, batch = _csr_arrays(key_lists, None, csr)
+        if batch == 0:
+            return [], []
+        out = ctypes.create_string_buffer(48 * batch)
+        ok = (ctypes.c_int32 * batch)()
+        _check(_lib.hbls_vote_key_sums(self._h, off, idx, batch, out, ok),
+               "vote_key_sums")
+        return [out.raw[48 * j:48 * (j + 1)] for j in range(batch)], list(ok)
+
+    def batch_verify_votes_multi(self, key_lists, sigs: bytes, msgs: bytes, mlen: int):
+        """batch_verify_votes for signer sets: vote j is checked against the
+        sum of its keys; a malformed key list gives HBLS_ERR_BADINPUT for
+        that vote."""
+        if len(sigs) % 96:
+            raise ValueError("sigs must be batch * 96 bytes")
+        off, idx, batch = _csr_arrays(key_lists, len(sigs) // 96)
+        if mlen <= 0 or len(msgs) != mlen * batch:
+            raise ValueError("msgs must be batch * mlen bytes")
+        res = (ctypes.c_int32 * batch)()
+        _check(_lib.hbls_batch_verify_votes_multi(self._h, off, idx, sigs, msgs, mlen,
+                                                  batch, res), "batch_verify_votes_multi")
+        return list(res)
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):
@@ -512,6 +591,25 @@ class Stream:
         res = (ctypes.c_int32 * batch)()
         _check(_lib.hbls_stream_process(self._h, ki, ri, sigs_cat, act,
                                         len(active), batch, res), "stream_process")
+        return list(res)
+
+    def process_multi(self, key_lists, round_idx, sigs_cat: bytes):
+        """process() for multi-key votes: vote j is signed by the keys
+        key_lists[j] (ascending committee indices) with one summed signature.
+        Per vote: 1 accepted (all bits set, signature added once), 2 valid but
+        one of its keys had voted (nothing set), 0 invalid, <0 malformed.
+        Votes take effect in list order."""
+        batch = len(round_idx)
+        if len(sigs_cat) != 96 * batch:
+            raise ValueError("key_lists/round_idx/sigs length mismatch")
+        off, idx, _ = _csr_arrays(key_lists, batch)
+        active = sorted(set(round_idx))
+        ri = (ctypes.c_uint32 * batch)(*round_idx)
+        act = (ctypes.c_uint32 * len(active))(*active)
+        res = (ctypes.c_int32 * batch)()
+        _check(_lib.hbls_stream_process_multi(self._h, off, idx, ri, sigs_cat, act,
+                                              len(active), batch, res),
+               "stream_process_multi")
         return list(res)
 
     def check(self, slots):

@@ -4149,6 +4149,7 @@ __global__ void k_stream_gather_check(const uint32_t *bitmap, int nwords, int bm
 #include "hbls_rlc.inc"
 #include "hbls_aggrlc.inc"
 #include "hbls_quorum.inc"
+#include "hbls_multikey.inc"
 
 extern "C" void hbls_stream_free(hbls_stream *s);
 

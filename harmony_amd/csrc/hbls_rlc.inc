@@ -65,6 +65,39 @@ __global__ void k_rlc_scale(const g1aff_t *table, int n, const uint32_t *key_idx
     results[i] = 1;
 }
 
+/* k_rlc_scale for multi-key votes (hbls_multikey.inc): the public key of
+ * vote i is its signer-set sum pks[i], pk_ok[i] != 1 marks a malformed signer
+ * set.  Unlike a table key a sum can be the point at infinity; such a vote
+ * never enters a combination (r*inf would hide its signature from the group
+ * check) and gets verify_pairing's identity edge directly: accepted only
+ * with an identity signature. */
+__global__ void k_rlc_scale_pk(const g1_t *pks, const int32_t *pk_ok,
+                               const uint32_t *grp, const int32_t *grp_ok,
+                               const g2aff_t *sigs, const int32_t *sig_flags,
+                               const int32_t *hm_ok, const uint64_t *scalars,
+                               g1_t *A, g2_t *B, int32_t *elig, int32_t *results,
+                               int batch) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch) return;
+    elig[i] = 0;
+    if (!grp_ok[i]) { results[i] = HBLS_ERR_BADINPUT; return; }
+    if (!hm_ok[grp[i]] || sig_flags[i] == 0 || pk_ok[i] != 1) {
+        results[i] = HBLS_ERR_BADINPUT; return;
+    }
+    g1_t pk = pks[i], a;
+    bool pub_inf = g1_is_inf(pk), sig_inf = sig_flags[i] == 2;
+    if (pub_inf || sig_inf) { results[i] = (pub_inf && sig_inf) ? 1 : 0; return; }
+    uint64_t r = scalars[i];
+    g1_mul(a, pk, &r, 1);
+    g2_t s, b;
+    g2_from_affine(s, sigs[i]);
+    g2_mul(b, s, &r, 1);
+    A[i] = a;
+    B[i] = b;
+    elig[i] = 1;
+    results[i] = 1;
+}
+
 /* one RLC_CHUNK-thread block per chunk: LDS tree over the chunk's eligible
  * A_i / B_i (k_stream_accum shape).  pcnt[c] = eligible votes in the chunk. */
 __global__ void __launch_bounds__(RLC_CHUNK) k_rlc_chunk_sum(
@@ -213,6 +246,27 @@ __global__ void k_verify_votes_sel(const uint32_t *sel, int nsel,
     results[i] = verify_pairing(pub, hms[h], sig_inf ? dummy : sigs[i], sig_inf);
 }
 
+/* k_verify_votes_sel for multi-key votes: public key from the signer-set
+ * sums.  Only eligible votes are listed, so neither point is infinity. */
+__global__ void k_verify_votes_sel_pk(const uint32_t *sel, int nsel,
+                                      const g1_t *pks, const int32_t *pk_ok,
+                                      const g2_t *hms, const uint32_t *hm_idx,
+                                      const g2aff_t *sigs,
+                                      const int32_t *sig_flags, const int32_t *hm_ok,
+                                      int32_t *results, int batch) {
+    int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nsel) return;
+    uint32_t i = sel[j];
+    if (i >= (uint32_t)batch) return;
+    int h = hm_idx ? (int)hm_idx[i] : (int)i;
+    if (!hm_ok[h] || sig_flags[i] == 0 || pk_ok[i] != 1) {
+        results[i] = HBLS_ERR_BADINPUT; return;
+    }
+    g2aff_t dummy;
+    bool sig_inf = sig_flags[i] == 2;
+    results[i] = verify_pairing(pks[i], hms[h], sig_inf ? dummy : sigs[i], sig_inf);
+}
+
 /* ---------------------------------------------------------------- host side */
 
 /* counters of the last batched call on this thread: groups pairing-checked,
@@ -267,13 +321,16 @@ static bool rlc_draw_scalars(uint64_t *out, size_t n) {
  *   d_saff / d_sflags decompressed signatures
  * Writes d_res for every vote whose group index is in range with the codes
  * k_verify_votes gives; the others get HBLS_ERR_BADINPUT (and the caller's
- * k_merge_pok says the same). */
+ * k_merge_pok says the same).
+ * d_pks != NULL (multi-key votes): vote i's public key is d_pks[i], valid
+ * where d_pk_ok[i] == 1, instead of table[d_idx[i]]; d_idx is not read. */
 static int rlc_verify_chain(const hbls_committee_t *c, const g2_t *d_hm,
                             const int32_t *d_hm_ok, size_t n_groups,
                             const uint32_t *h_grp, const uint32_t *d_idx,
                             const uint32_t *d_grp, const int32_t *d_grp_ok,
                             const g2aff_t *d_saff, const int32_t *d_sflags,
-                            int32_t *d_res, size_t batch) {
+                            int32_t *d_res, size_t batch,
+                            const g1_t *d_pks = nullptr, const int32_t *d_pk_ok = nullptr) {
     /* counting sort by group: perm, chunks, groups */
     std::vector<uint32_t> gcount(n_groups, 0);
     size_t nperm = 0;
@@ -332,10 +389,16 @@ static int rlc_verify_chain(const hbls_committee_t *c, const g2_t *d_hm,
     const uint32_t *d_gcs = d_gid + ng, *d_gcc = d_gcs + ng;
 
     int nb = (int)((batch + 63) / 64);
-    hipLaunchKernelGGL(k_rlc_scale, dim3(nb), dim3(64), 0, 0,
-                       c->d_table, (int)c->n, d_idx, d_grp, d_grp_ok, d_saff, d_sflags,
-                       d_hm_ok, dsc.as<uint64_t>(), dA.as<g1_t>(), dB.as<g2_t>(),
-                       delig.as<int32_t>(), d_res, (int)batch);
+    if (d_pks)
+        hipLaunchKernelGGL(k_rlc_scale_pk, dim3(nb), dim3(64), 0, 0,
+                           d_pks, d_pk_ok, d_grp, d_grp_ok, d_saff, d_sflags,
+                           d_hm_ok, dsc.as<uint64_t>(), dA.as<g1_t>(), dB.as<g2_t>(),
+                           delig.as<int32_t>(), d_res, (int)batch);
+    else
+        hipLaunchKernelGGL(k_rlc_scale, dim3(nb), dim3(64), 0, 0,
+                           c->d_table, (int)c->n, d_idx, d_grp, d_grp_ok, d_saff, d_sflags,
+                           d_hm_ok, dsc.as<uint64_t>(), dA.as<g1_t>(), dB.as<g2_t>(),
+                           delig.as<int32_t>(), d_res, (int)batch);
     if (!ng) { HIP_OK(hipGetLastError()); return HBLS_OK; }
     hipLaunchKernelGGL(k_rlc_chunk_sum, dim3((uint32_t)nc), dim3(RLC_CHUNK), 0, 0,
                        d_perm, (int)nperm, d_cstart, d_ccnt, (int)nc,
@@ -407,9 +470,14 @@ static int rlc_verify_chain(const hbls_committee_t *c, const g2_t *d_hm,
     DevBuf dvsel(nv * 4);
     if (dvsel.err) return HBLS_ERR;
     HIP_OK(hipMemcpy(dvsel.p, vsel.data(), nv * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_verify_votes_sel, dim3((uint32_t)((nv + 63) / 64)), dim3(64), 0, 0,
-                       dvsel.as<uint32_t>(), (int)nv, c->d_table, (int)c->n, d_idx,
-                       d_hm, d_grp, d_saff, d_sflags, d_hm_ok, d_res, (int)batch);
+    if (d_pks)
+        hipLaunchKernelGGL(k_verify_votes_sel_pk, dim3((uint32_t)((nv + 63) / 64)), dim3(64), 0, 0,
+                           dvsel.as<uint32_t>(), (int)nv, d_pks, d_pk_ok,
+                           d_hm, d_grp, d_saff, d_sflags, d_hm_ok, d_res, (int)batch);
+    else
+        hipLaunchKernelGGL(k_verify_votes_sel, dim3((uint32_t)((nv + 63) / 64)), dim3(64), 0, 0,
+                           dvsel.as<uint32_t>(), (int)nv, c->d_table, (int)c->n, d_idx,
+                           d_hm, d_grp, d_saff, d_sflags, d_hm_ok, d_res, (int)batch);
     HIP_OK(hipGetLastError());
     return HBLS_OK;
 }

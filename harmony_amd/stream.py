@@ -16,6 +16,34 @@ aggregation launches) capped at ~3.4k msgs/s; this is the round-2 redesign.
 from . import core
 
 
+def ordered_claim_model(bitmaps, tick):
+    """Pure-Python model of the multi-key tick's ordered all-or-nothing rule
+    (hbls_stream_process_multi; the reference's
+    drop-if-any-key-voted check, leader.go:127-135, followed by SetKeysAtomic).
+
+    bitmaps: the rounds' current bitmaps, a list of bytes indexed by round.
+    tick: (round, keys, valid) per vote in batch order; valid is the verify
+    stage's verdict — True/1 for a valid signature, False/0 for an invalid
+    one, or a negative code for a malformed vote.
+    Returns (results, new_bitmaps): a valid vote gets 1 and sets all its bits
+    when none of them is set at its turn, else 2 and sets nothing; any other
+    vote keeps its verdict as its result."""
+    new = [bytearray(b) for b in bitmaps]
+    results = []
+    for r, keys, valid in tick:
+        if int(valid) != 1:
+            results.append(int(valid))
+            continue
+        bm = new[r]
+        if any(bm[k >> 3] & (1 << (k & 7)) for k in keys):
+            results.append(2)
+            continue
+        for k in keys:
+            bm[k >> 3] |= 1 << (k & 7)
+        results.append(1)
+    return results, [bytes(b) for b in new]
+
+
 class StreamVerifier:
     """Single-round stream (window-checked).  External API kept from round 1:
     process_batch / final_check / accepted / rejected / bitmap / agg_sig."""
@@ -142,11 +170,21 @@ class MultiStreamVerifier:
         """votes: list of (round_idx, key_idx, sig96 bytes).  One device
         tick; per-round bookkeeping from the downloaded results.  Rounds
         whose message count crosses the window get ONE batched pairing
-        check (the 'periodic batch pairing' of BASELINE configs[4])."""
+        check (the 'periodic batch pairing' of BASELINE configs[4]).
+
+        key_idx may be a tuple of ascending indices for a multi-key sender
+        (one summed signature, consensus/construct.go:99-114); a tick that
+        holds any tuple goes through the multi-key entry, where votes take
+        effect in list order and a vote with an already-voted key sets
+        nothing."""
         key_idx = [v[1] for v in votes]
         round_idx = [v[0] for v in votes]
         sigs = b"".join(v[2] for v in votes)
-        res = self.stream.process(key_idx, round_idx, sigs)
+        if any(isinstance(k, tuple) for k in key_idx):
+            res = self.stream.process_multi(
+                [k if isinstance(k, tuple) else (k,) for k in key_idx], round_idx, sigs)
+        else:
+            res = self.stream.process(key_idx, round_idx, sigs)
         for (r, _i, _s), ok in zip(votes, res):
             if ok == 1:
                 self.rounds[r].accepted += 1

@@ -296,6 +296,51 @@ int hbls_stream_get(hbls_stream_t *s, uint32_t slot, uint8_t *bitmap_out,
 int hbls_stream_power(hbls_stream_t *s, const uint32_t *slots, int k,
                       uint64_t *power_out, uint32_t *count_out, int32_t *quorum_out);
 
+/* ---- multi-key votes ----
+ * A node that runs several BLS keys sends one message per phase: one
+ * signature, the sum of its keys' signatures (consensus/construct.go:99-114),
+ * under a sender bitmap (SenderPubkeyBitmap, fbft_log.go:334-347).  Signer
+ * sets cross the ABI in CSR form: vote j is signed by
+ * key_idx[key_off[j] .. key_off[j+1]); key_off has batch + 1 entries, starts
+ * at 0 and never decreases (else the call fails with HBLS_ERR_BADINPUT, before
+ * any upload); the indices of one vote are strictly ascending, the order
+ * GetSignedPubKeysFromBitmap yields (crypto/bls/mask.go:176-194).  A vote whose
+ * list is empty, holds an index >= n or is not strictly ascending is malformed:
+ * it gets HBLS_ERR_BADINPUT as its per-vote code, decided on the device before
+ * any index is used as an address. */
+
+/* signerPubKey.Add over each vote's keys (leader.go:165-172, :279-286):
+ * out48s[j] = serialized key sum, ok[j] = 1; a sum that is the point at
+ * infinity is 48 zero bytes, as in hbls_mask_aggregate_g1.  A malformed vote
+ * has ok[j] = HBLS_ERR_BADINPUT and a zero block. */
+int hbls_vote_key_sums(const hbls_committee_t *c, const uint32_t *key_off,
+                       const uint32_t *key_idx, size_t batch,
+                       uint8_t *out48s, int32_t *ok);
+
+/* hbls_batch_verify_votes for signer sets: results[j] is what
+ * hbls_verify_hash(sum of vote j's keys, sig_j, msg_j) returns, herumi's
+ * identity edges included (an infinity key sum accepts the identity signature
+ * and nothing else). */
+int hbls_batch_verify_votes_multi(const hbls_committee_t *c, const uint32_t *key_off,
+                                  const uint32_t *key_idx, const uint8_t *sigs96,
+                                  const uint8_t *msgs, size_t msg_len, size_t batch,
+                                  int32_t *results);
+
+/* hbls_stream_process for signer sets; results[j]: 1 accepted — all of the
+ * vote's bits are set (SetKeysAtomic, mask.go:226-242) and its signature is
+ * added once to the round's aggregate; 2 valid, but at least one of its keys
+ * had already voted in that round — no bit is set, nothing is added
+ * (leader.go:127-135, :227-235); 0 invalid signature; <0 malformed.  Votes
+ * of one tick take effect as if applied in ascending batch index (the
+ * reference's arrival order under its mutex): {1,2}, {2,3}, {3,4} give 1, 2, 1.
+ * active_slots lists the distinct round slots present in the batch; a repeated
+ * slot, or an in-range round of the batch that is not listed, fails the call.
+ * Honours hbls_stream_set_verify_mode, with equal results in both modes. */
+int hbls_stream_process_multi(hbls_stream_t *s, const uint32_t *key_off,
+                              const uint32_t *key_idx, const uint32_t *round_idx,
+                              const uint8_t *sigs96, const uint32_t *active_slots,
+                              int n_active, size_t batch, int32_t *results);
+
 /* ---- combined aggregate verify ----
  * How hbls_batch_agg_verify / hbls_batch_seal_verify run their pairing stage:
  *   0  exact: one final exponentiation per item
