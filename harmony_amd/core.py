@@ -117,6 +117,10 @@ def _load():
     lib.hbls_set_aggrlc_threshold.restype = None
     lib.hbls_aggrlc_last_stats.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
     lib.hbls_aggrlc_last_stats.restype = None
+    lib.hbls_set_aggrlc_final.argtypes = [ctypes.c_int]
+    lib.hbls_aggrlc_final_selftest.argtypes = [ctypes.c_int]
+    lib.hbls_last_host_ns.restype = ctypes.c_uint64
+    lib.hbls_last_host_ns.argtypes = [ctypes.c_int]
     u64p, u32p, i32p = (ctypes.POINTER(t) for t in
                         (ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32))
     lib.hbls_committee_set_quorum.argtypes = [ctypes.c_void_p, u64p, ctypes.c_uint64]
@@ -218,6 +222,26 @@ def aggrlc_last_stats():
     out = (ctypes.c_uint32 * 3)()
     _lib.hbls_aggrlc_last_stats(out)
     return list(out)
+
+
+def set_aggrlc_final(kernel: int):
+    """kernel of the combined path's final exponentiations: 16 or 8 = four
+    lanes per chunk, that many chunks per block; 0 = one lane per chunk; -1
+    restores the default.  Verdicts do not depend on it."""
+    _check(_lib.hbls_set_aggrlc_final(kernel), "set_aggrlc_final")
+
+
+def aggrlc_final_selftest(nchunks: int) -> int:
+    """chunks on which the cooperative final kernels and the one-lane kernel
+    disagree over nchunks deterministic chunk products (0 = parity)"""
+    return _check(_lib.hbls_aggrlc_final_selftest(nchunks), "aggrlc_final_selftest")
+
+
+def last_host_ns(i: int) -> int:
+    """host-side time of the last aggregate-verify call on this thread:
+    0 device allocations, 1 inside upload calls, 2 first launch to results
+    on the host, 3 frees, 4 the whole call"""
+    return _lib.hbls_last_host_ns(i)
 
 
 def pk_from_sk(sk32: bytes) -> bytes:

@@ -137,6 +137,49 @@ __global__ void k_aggrlc_final(const fp12_t *FC, const int32_t *ccnt,
     verdict[c] = fp12_is_one(f) ? 1 : 0;
 }
 
+/* the same contract on four lanes per chunk (hbls_coop.inc): ITEMS chunks per
+ * block in the arena layout of k_verify_coop.  The thread-per-chunk kernel
+ * above costs one whole final exponentiation's latency on nchunks/64 lone
+ * waves; here nchunks/ITEMS one-wave blocks spread over the chip and each
+ * runs the cooperative chain.  cv_final_exp returns the same field element
+ * as final_exp, so the verdicts are identical.  Chunks that need no
+ * exponentiation, and the dummy sub-items of the last block, march through
+ * the chain on fp12 one: control flow stays uniform across every barrier. */
+template <int ITEMS>
+__global__ void __launch_bounds__(ITEMS * CV_LANES) k_aggrlc_final_coop(
+        const fp12_t *FC, const int32_t *ccnt, const int32_t *cforce,
+        int32_t *verdict, int nchunks) {
+    __shared__ uint64_t arena[ITEMS][CV_STRIDE64];
+    __shared__ int32_t pre[ITEMS];   /* -2 compute; -1 dummy; else the verdict */
+    const int sub = threadIdx.x / CV_LANES;
+    const int q = threadIdx.x % CV_LANES;
+    const int c = blockIdx.x * ITEMS + sub;
+    lds_fp2 *A = (lds_fp2 *)arena[sub];
+    if (q == 0) {
+        int32_t r = -2;
+        if (c >= nchunks) r = -1;
+        else if (cforce[c]) r = 0;
+        else if (ccnt[c] == 0) r = 1;
+        pre[sub] = r;
+        fp12_t f;
+        if (r == -2) f = FC[c];
+        else fp12_one(f);
+        cv_st_fp12(A, CV_F0, f);
+    }
+    __syncthreads();
+    cv_fp12_conj(A, q, CV_F0, CV_F0);
+    cv_final_exp(A, q);
+    if (q == 0) {
+        int32_t r = pre[sub];
+        if (r == -2) {
+            fp12_t f;
+            cv_ld_fp12(A, CV_F0, f);
+            r = fp12_is_one(f) ? 1 : 0;
+        }
+        if (r != -1) verdict[c] = r;
+    }
+}
+
 /* k_verify over a compacted index list (the eligible items of failing chunks) */
 __global__ void k_verify_sel(const uint32_t *sel, int nsel, const g1_t *aggpubs,
                              const g2_t *hms, const g2aff_t *sigs,
@@ -166,8 +209,10 @@ static void aggrlc_stats_reset(void) {
 extern "C" int hbls_aggrlc_chunk_size(void) { return AGGRLC_CHUNK; }
 
 static int g_agg_verify_mode = -2;      /* -2: read env on first use */
-/* smallest batch the auto mode sends to the combined path (DESIGN.md §4e) */
-#define AGGRLC_DEFAULT_THRESHOLD 131072
+/* smallest batch the auto mode sends to the combined path: the smallest one
+ * measured, with the cooperative tail (DESIGN.md §4h; 131072 with the
+ * one-lane tail, §4e) */
+#define AGGRLC_DEFAULT_THRESHOLD 16384
 static int g_aggrlc_threshold = AGGRLC_DEFAULT_THRESHOLD;
 static int agg_verify_mode(void) {
     if (g_agg_verify_mode == -2) {
@@ -184,6 +229,118 @@ extern "C" int hbls_set_agg_verify_mode(int mode) {
 }
 extern "C" void hbls_set_aggrlc_threshold(int n) {
     g_aggrlc_threshold = n < 0 ? AGGRLC_DEFAULT_THRESHOLD : n;
+}
+
+/* which kernel runs the chunks' final exponentiations: 16 or 8 = cooperative
+ * with that many chunks per block, 0 = one lane per chunk (the measured
+ * loser at 4096 chunks, DESIGN.md §4h, kept reproducible) */
+#define AGGRLC_FINAL_DEFAULT 16
+static int g_aggrlc_final = -2;         /* -2: read env on first use */
+static int aggrlc_final_kernel(void) {
+    if (g_aggrlc_final == -2) {
+        const char *e = getenv("HBLS_AGGRLC_FINAL");
+        int k = e ? atoi(e) : AGGRLC_FINAL_DEFAULT;
+        g_aggrlc_final = (k == 0 || k == 8 || k == 16) ? k : AGGRLC_FINAL_DEFAULT;
+    }
+    return g_aggrlc_final;
+}
+extern "C" int hbls_set_aggrlc_final(int kernel) {
+    if (kernel == -1) kernel = AGGRLC_FINAL_DEFAULT;
+    if (kernel != 0 && kernel != 8 && kernel != 16) return HBLS_ERR_BADINPUT;
+    g_aggrlc_final = kernel;
+    return HBLS_OK;
+}
+static void launch_aggrlc_final(int kernel, const fp12_t *d_FC, const int32_t *d_ccnt,
+                                const int32_t *d_cforce, int32_t *d_verdict, int nc) {
+    if (kernel == 16)
+        hipLaunchKernelGGL(k_aggrlc_final_coop<16>, dim3((uint32_t)((nc + 15) / 16)),
+                           dim3(16 * CV_LANES), 0, 0, d_FC, d_ccnt, d_cforce, d_verdict, nc);
+    else if (kernel == 8)
+        hipLaunchKernelGGL(k_aggrlc_final_coop<8>, dim3((uint32_t)((nc + 7) / 8)),
+                           dim3(8 * CV_LANES), 0, 0, d_FC, d_ccnt, d_cforce, d_verdict, nc);
+    else
+        hipLaunchKernelGGL(k_aggrlc_final, dim3((uint32_t)((nc + 63) / 64)), dim3(64), 0, 0,
+                           d_FC, d_ccnt, d_cforce, d_verdict, nc);
+}
+
+/* selftest inputs, chunk c by c % 8:
+ *   0, 6, 7  arbitrary nonzero element          -> computed, verdict 0
+ *   1        element of the Fp6 subfield (c1=0) -> computed, verdict 1 (the
+ *            easy part of the exponentiation sends the subfield to one)
+ *   2        fp12 one                           -> computed, verdict 1
+ *   3        arbitrary, ccnt == 0               -> verdict 1 without computing
+ *   4        arbitrary, cforce set              -> verdict 0 without computing
+ *   5        Fp6 subfield, cforce set           -> verdict 0 (cforce comes first)
+ * The coefficients are small multiples of one pushed through two squarings,
+ * so they are reduced field elements with no structure the chain could
+ * exploit. */
+__global__ void k_aggrlc_final_fill(fp12_t *FC, int32_t *ccnt, int32_t *cforce, int nchunks) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nchunks) return;
+    int kind = c % 8;
+    fp_t one;
+    fp_one(one);
+    fp_t co[12];
+    for (int k = 0; k < 12; k++) {
+        fp_t t;
+        fp_zero(t);
+        uint32_t m = (uint32_t)c * 12u + (uint32_t)k + 3u;
+        for (int b = 31; b >= 0; b--) {
+            fp_dbl(t, t);
+            if ((m >> b) & 1u) fp_add(t, t, one);
+        }
+        fp_sqr(t, t);
+        fp_add(t, t, one);
+        fp_sqr(t, t);
+        co[k] = t;
+    }
+    fp12_t f;
+    fp2_t *s = &f.c0.c0;                /* six fp2 coefficients, c0 then c1 */
+    for (int k = 0; k < 6; k++) { s[k].a = co[2 * k]; s[k].b = co[2 * k + 1]; }
+    if (kind == 1 || kind == 5)
+        for (int k = 3; k < 6; k++) { fp_zero(s[k].a); fp_zero(s[k].b); }
+    if (kind == 2) fp12_one(f);
+    FC[c] = f;
+    ccnt[c] = kind == 3 ? 0 : 1 + c % 64;
+    cforce[c] = (kind == 4 || kind == 5) ? 1 : 0;
+}
+
+/* both final kernels (the cooperative one at 16 and at 8 chunks per block)
+ * on the inputs above: the number of chunk verdicts on which a cooperative
+ * launch differs from the thread-per-chunk one (0 = parity), HBLS_ERR when
+ * the thread-per-chunk verdicts are not what the input kinds dictate — in
+ * particular when they are not a mix of 0 and 1 from two chunks up (a lone
+ * chunk has a single verdict). */
+extern "C" int hbls_aggrlc_final_selftest(int nchunks) {
+    int rc = require_gpu();
+    if (rc != HBLS_OK) return rc;
+    if (nchunks < 1 || nchunks > (1 << 20)) return HBLS_ERR_BADINPUT;
+    size_t nc = (size_t)nchunks;
+    DevBuf dFC(nc * sizeof(fp12_t)), dcs(2 * nc * 4), dv(3 * nc * 4);
+    if (dFC.err || dcs.err || dv.err) return HBLS_ERR;
+    int32_t *d_ccnt = dcs.as<int32_t>(), *d_cforce = d_ccnt + nc;
+    HIP_OK(hipMemset(dv.p, 0xff, 3 * nc * 4));      /* -1: verdict never stored */
+    hipLaunchKernelGGL(k_aggrlc_final_fill, dim3((uint32_t)((nc + 63) / 64)), dim3(64), 0, 0,
+                       dFC.as<fp12_t>(), d_ccnt, d_cforce, nchunks);
+    const int kernels[3] = { 0, 16, 8 };
+    for (int k = 0; k < 3; k++)
+        launch_aggrlc_final(kernels[k], dFC.as<fp12_t>(), d_ccnt, d_cforce,
+                            dv.as<int32_t>() + k * nc, nchunks);
+    HIP_OK(hipGetLastError());
+    std::vector<int32_t> v(3 * nc);
+    HIP_OK(hipMemcpy(v.data(), dv.p, 3 * nc * 4, hipMemcpyDeviceToHost));
+    int zeros = 0, ones = 0;
+    for (size_t c = 0; c < nc; c++) {
+        int kind = (int)(c % 8);
+        int want = (kind == 1 || kind == 2 || kind == 3) ? 1 : 0;
+        if (v[c] != want) return HBLS_ERR;
+        if (v[c]) ones++; else zeros++;
+    }
+    if (nc >= 2 && (!zeros || !ones)) return HBLS_ERR;
+    int diff = 0;
+    for (size_t c = 0; c < nc; c++)
+        if (v[nc + c] != v[c] || v[2 * nc + c] != v[c]) diff++;
+    return diff;
 }
 
 /* fixed-base window table of -G1: gtab[w*255 + b-1] = b * 2^(8w) * (-G1) */
@@ -231,13 +388,22 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
     size_t nc = (batch + AGGRLC_CHUNK - 1) / AGGRLC_CHUNK;
     std::vector<uint64_t> scalars(batch);
     if (!rlc_draw_scalars(scalars.data(), batch)) return AGGRLC_FALLBACK;
+    FreeClock fclk;
+    uint64_t t_alloc = host_now_ns();
     DevBuf dsc(batch * 8), dF(batch * sizeof(fp12_t)), delig(batch * 4);
     DevBuf dFC(nc * sizeof(fp12_t)), dcs(3 * nc * 4);
+    g_host_ns[0] += host_now_ns() - t_alloc;
+    FreeClockArm farm(fclk);
     if (dsc.err || dF.err || delig.err || dFC.err || dcs.err) {
         (void)hipGetLastError();
         return AGGRLC_FALLBACK;
     }
-    HIP_OK(hipMemcpy(dsc.p, scalars.data(), batch * 8, hipMemcpyHostToDevice));
+    /* the scalars go up beside the kernels already queued, not behind them;
+     * `scalars` outlives the copy (the verdict download below waits for the
+     * Miller kernel, which waits for the upload) */
+    EventSet<1> up;
+    if (up.err != hipSuccess) return HBLS_ERR;
+    HIP_OK(upload_then_wait(dsc.p, scalars.data(), batch * 8, up[0]));
     int32_t *d_ccnt = dcs.as<int32_t>(), *d_cforce = d_ccnt + nc, *d_verdict = d_cforce + nc;
     hipEvent_t ev[4];
     for (int i = 0; i < 4; i++) (void)hipEventCreate(&ev[i]);
@@ -250,8 +416,8 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
                        dF.as<fp12_t>(), delig.as<int32_t>(), (int)batch, (int)nc,
                        dFC.as<fp12_t>(), d_ccnt, d_cforce);
     (void)hipEventRecord(ev[2], 0);
-    hipLaunchKernelGGL(k_aggrlc_final, dim3((uint32_t)((nc + 63) / 64)), dim3(64), 0, 0,
-                       dFC.as<fp12_t>(), d_ccnt, d_cforce, d_verdict, (int)nc);
+    launch_aggrlc_final(aggrlc_final_kernel(), dFC.as<fp12_t>(), d_ccnt, d_cforce,
+                        d_verdict, (int)nc);
     (void)hipEventRecord(ev[3], 0);
     std::vector<int32_t> hc(3 * nc);
     hipError_t e = hipMemcpy(hc.data(), dcs.p, 3 * nc * 4, hipMemcpyDeviceToHost);

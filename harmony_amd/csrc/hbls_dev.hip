@@ -2392,6 +2392,96 @@ struct DevBuf {
     template <typename T> T *as() const { return (T *)p; }
 };
 
+/* ---- host-side accounting of the last aggregate-verify call on this thread
+ * (steady_clock): 0 device allocations, 1 time inside upload calls, 2 first
+ * launch to results on the host, 3 frees, 4 the whole call */
+#include <chrono>
+static thread_local uint64_t g_host_ns[5] = {0};
+static thread_local bool g_host_open = false;
+static inline uint64_t host_now_ns(void) {
+    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
+        std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+extern "C" uint64_t hbls_last_host_ns(int i) { return (i >= 0 && i < 5) ? g_host_ns[i] : 0; }
+/* adds its own lifetime to counter i */
+struct HostSpan {
+    int i; uint64_t t0;
+    explicit HostSpan(int idx) : i(idx), t0(host_now_ns()) {}
+    ~HostSpan() { g_host_ns[i] += host_now_ns() - t0; }
+};
+/* the outermost one on a thread resets the counters and owns counter 4 */
+struct HostCall {
+    bool owner; uint64_t t0;
+    HostCall() : owner(!g_host_open), t0(0) {
+        if (!owner) return;
+        g_host_open = true;
+        for (int i = 0; i < 5; i++) g_host_ns[i] = 0;
+        t0 = host_now_ns();
+    }
+    ~HostCall() {
+        if (!owner) return;
+        g_host_ns[4] = host_now_ns() - t0;
+        g_host_open = false;
+    }
+};
+/* times the destructors of the DevBufs declared between the two: FreeClock
+ * before the first of them, FreeClockArm after the last (locals die in
+ * reverse order, so the arm fires first and the clock stops last) */
+struct FreeClock {
+    uint64_t t0 = 0; bool armed = false;
+    ~FreeClock() { if (armed) g_host_ns[3] += host_now_ns() - t0; }
+};
+struct FreeClockArm {
+    FreeClock &fc;
+    explicit FreeClockArm(FreeClock &f) : fc(f) {}
+    ~FreeClockArm() { fc.t0 = host_now_ns(); fc.armed = true; }
+};
+
+/* ---- uploads off the compute stream.  Kernels run on the null stream; a
+ * host buffer goes up on one non-blocking stream of its own (created on
+ * first use, kept for the life of the process) with an event behind it, and
+ * the null stream waits on that event ahead of the first kernel that reads
+ * the buffer — so a kernel waits only for the bytes it reads.  The sources
+ * are pageable: the copy call returns once the runtime has staged them, and
+ * the host issues the next launch only then, which is why the callers
+ * interleave uploads and launches instead of queueing every upload first. */
+static hipStream_t g_upload_stream = nullptr;
+static std::once_flag g_upload_flag;
+static hipStream_t upload_stream(void) {
+    std::call_once(g_upload_flag, [] {
+        hipStream_t s = nullptr;
+        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess)
+            g_upload_stream = s;
+        else
+            (void)hipGetLastError();    /* no stream: uploads fall to the null stream */
+    });
+    return g_upload_stream;
+}
+/* dst <- src on the upload stream, `done` recorded behind it, and the null
+ * stream made to wait on `done` */
+static hipError_t upload_then_wait(void *dst, const void *src, size_t n, hipEvent_t done) {
+    HostSpan sp(1);
+    hipStream_t s = upload_stream();
+    hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipEventRecord(done, s);
+    if (e == hipSuccess) e = hipStreamWaitEvent(0, done, 0);
+    return e;
+}
+/* a fixed set of events, destroyed on every return path */
+template <int N> struct EventSet {
+    hipEvent_t e[N];
+    hipError_t err = hipSuccess;
+    EventSet() {
+        for (int i = 0; i < N; i++) {
+            e[i] = nullptr;
+            hipError_t r = hipEventCreate(&e[i]);
+            if (r != hipSuccess) err = r;
+        }
+    }
+    ~EventSet() { for (int i = 0; i < N; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
+    hipEvent_t operator[](int i) const { return e[i]; }
+};
+
 struct Timer {
     hipEvent_t a, b;
     Timer() { hipEventCreate(&a); hipEventCreate(&b); hipEventRecord(a, 0); }
@@ -2701,26 +2791,45 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
                          int32_t *d_res, size_t batch);
 #define AGGRLC_FALLBACK 2       /* aggrlc_verify wrote nothing: run the exact path */
 
+/* host copies of the three inputs, for the entry point whose inputs are not
+ * on the device yet */
+struct AggHostSrc { const uint8_t *bitmaps, *sigs, *msgs; };
+
 /* the four-stage aggregate-verify pipeline over DEVICE-resident inputs
  * (bitmaps, serialized sigs, messages) — shared by the host-buffer entry
- * points and the HBM-direct seal-blob path. */
+ * points and the HBM-direct seal-blob path.  Launch order: hash (reads the
+ * messages), decompress (the signatures), mask (the bitmaps), verify.  With
+ * `src` the three device buffers are still empty and each is uploaded just
+ * ahead of the stage that reads it, so the large bitmap upload arrives
+ * behind the hash and decompress kernels instead of in front of them.
+ * g_stage_ns[0..3] stay mask, hash, decompress, verify: each the interval
+ * between events recorded around that stage's launches (an upload wait sits
+ * before the stage's first event). */
 static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_bm,
                                    const uint8_t *d_sig, const uint8_t *d_msg,
-                                   size_t msg_len, size_t batch, int32_t *results) {
+                                   size_t msg_len, size_t batch, int32_t *results,
+                                   const AggHostSrc *src = nullptr) {
+    HostCall hcall;
     size_t bm = (c->n + 7) / 8;
+    FreeClock fclk;
+    uint64_t t_alloc = host_now_ns();
     DevBuf dagg(batch * sizeof(g1_t)), dhm(batch * sizeof(g2_t));
     DevBuf dsaff(batch * sizeof(g2aff_t)), dsflags(batch * 4), dhok(batch * 4), dres(batch * 4);
+    g_host_ns[0] += host_now_ns() - t_alloc;
+    FreeClockArm farm(fclk);
     if (dagg.err || dhm.err || dsaff.err || dsflags.err || dhok.err || dres.err)
         return HBLS_ERR;
     int nb = (int)((batch + 63) / 64);
     aggrlc_stats_reset();
-    hipEvent_t ev[5];
-    for (int i = 0; i < 5; i++) (void)hipEventCreate(&ev[i]);
-    (void)hipEventRecord(ev[0], 0);
-    launch_mask_aggregate(c->d_table, (int)c->n, d_bm, (int)bm,
-                                         c->d_full_sum, dagg.as<g1_t>(), (int)batch,
-                                         c->d_wtab, c->d_winf);
-    (void)hipEventRecord(ev[1], 0);
+    for (int i = 4; i < 7; i++) g_stage_ns[i] = 0;    /* the combined path's own, if it runs */
+    /* ev[2s], ev[2s+1] around stage s (0 mask, 1 hash, 2 decompress, 3 verify) */
+    EventSet<8> ev;
+    EventSet<3> up;
+    if (ev.err != hipSuccess || up.err != hipSuccess) return HBLS_ERR;
+    uint64_t t_launch = host_now_ns();
+
+    if (src) HIP_OK(upload_then_wait((void *)d_msg, src->msgs, batch * msg_len, up[0]));
+    (void)hipEventRecord(ev[2], 0);
     if ((int)batch <= coop_threshold()) {
         int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
         LAUNCH_COOP(k_hash_to_g2_coop, batch, d_msg, (int)msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(),
@@ -2730,7 +2839,10 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
                            d_msg, (int)msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(),
                            (int)batch, g_fast_cofactor);
     }
-    (void)hipEventRecord(ev[2], 0);
+    (void)hipEventRecord(ev[3], 0);
+
+    if (src) HIP_OK(upload_then_wait((void *)d_sig, src->sigs, batch * 96, up[1]));
+    (void)hipEventRecord(ev[4], 0);
     if ((int)batch <= coop_threshold()) {
         int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
         LAUNCH_COOP(k_g2_decompress_coop, batch, d_sig, dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
@@ -2738,7 +2850,16 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
         hipLaunchKernelGGL(k_g2_decompress, dim3(nb), dim3(64), 0, 0,
                            d_sig, dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
     }
-    (void)hipEventRecord(ev[3], 0);
+    (void)hipEventRecord(ev[5], 0);
+
+    if (src) HIP_OK(upload_then_wait((void *)d_bm, src->bitmaps, batch * bm, up[2]));
+    (void)hipEventRecord(ev[0], 0);
+    launch_mask_aggregate(c->d_table, (int)c->n, d_bm, (int)bm,
+                                         c->d_full_sum, dagg.as<g1_t>(), (int)batch,
+                                         c->d_wtab, c->d_winf);
+    (void)hipEventRecord(ev[1], 0);
+
+    (void)hipEventRecord(ev[6], 0);
     int arc = AGGRLC_FALLBACK;
     if (aggrlc_wanted(batch)) {
         arc = aggrlc_verify(dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
@@ -2768,18 +2889,18 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
         LAUNCH_VERIFY_SCALAR(nb, dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
                            dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), (int)batch);
     }
-    (void)hipEventRecord(ev[4], 0);
-    HIP_OK(hipEventSynchronize(ev[4]));
+    (void)hipEventRecord(ev[7], 0);
+    HIP_OK(hipEventSynchronize(ev[7]));
     float ms_total = 0, ms = 0;
-    (void)hipEventElapsedTime(&ms_total, ev[0], ev[4]);
+    (void)hipEventElapsedTime(&ms_total, ev[2], ev[7]);
     g_last_ns = (uint64_t)(ms_total * 1e6);
     for (int i = 0; i < 4; i++) {
-        (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
+        (void)hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]);
         g_stage_ns[i] = (uint64_t)(ms * 1e6);
     }
-    for (int i = 0; i < 5; i++) (void)hipEventDestroy(ev[i]);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(results, dres.p, batch * 4, hipMemcpyDeviceToHost));
+    g_host_ns[2] += host_now_ns() - t_launch;
     return HBLS_OK;
 }
 
@@ -2788,14 +2909,18 @@ extern "C" int hbls_batch_agg_verify(const hbls_committee_t *c, const uint8_t *b
                                      size_t msg_len, size_t batch, int32_t *results) {
     int rc = require_gpu();
     if (rc != HBLS_OK) return rc;
+    HostCall hcall;
     size_t bm = (c->n + 7) / 8;
+    FreeClock fclk;
+    uint64_t t_alloc = host_now_ns();
     DevBuf dbm(batch * bm), dsig(batch * 96), dmsg(batch * msg_len);
+    g_host_ns[0] += host_now_ns() - t_alloc;
+    FreeClockArm farm(fclk);
     if (dbm.err || dsig.err || dmsg.err) return HBLS_ERR;
-    HIP_OK(hipMemcpy(dbm.p, bitmaps, batch * bm, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(dsig.p, sigs96, batch * 96, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(dmsg.p, msgs, batch * msg_len, hipMemcpyHostToDevice));
+    /* the pipeline uploads each buffer ahead of the stage that reads it */
+    AggHostSrc src = { bitmaps, sigs96, msgs };
     return run_agg_verify_pipeline(c, dbm.as<uint8_t>(), dsig.as<uint8_t>(),
-                                   dmsg.as<uint8_t>(), msg_len, batch, results);
+                                   dmsg.as<uint8_t>(), msg_len, batch, results, &src);
 }
 
 extern "C" int hbls_agg_verify(const hbls_committee_t *c, const uint8_t *bitmap,

@@ -362,6 +362,18 @@ int hbls_aggrlc_chunk_size(void);
 /* chunks checked, chunks failed, items re-checked per item — of the last
  * aggregate-verify call on this thread (zeros when it ran exact) */
 void hbls_aggrlc_last_stats(uint32_t out[3]);
+/* the kernel that runs the chunks' final exponentiations on the combined
+ * path: 16 or 8 = four lanes per chunk with that many chunks
+ * per block, 0 = one lane per chunk, -1 restores the default (16).  Verdicts
+ * are the same for every choice.  Other values return HBLS_ERR_BADINPUT.
+ * The environment variable HBLS_AGGRLC_FINAL (0/8/16) sets the initial one. */
+int hbls_set_aggrlc_final(int kernel);
+/* runs every final kernel on nchunks deterministic chunk products (arbitrary
+ * elements, Fp6-subfield elements, one; empty and forced chunks) and returns
+ * the number of chunks on which a cooperative launch and the one-lane kernel
+ * disagree (0 = parity); HBLS_ERR if the one-lane verdicts are not the ones
+ * the inputs dictate, a mix of 0 and 1 from two chunks up. */
+int hbls_aggrlc_final_selftest(int nchunks);
 
 /* batch Keccak-256 (consensus message digests, crypto/hash/hash.go:9-15) */
 int hbls_batch_keccak256(const uint8_t *msgs, size_t msg_len, size_t batch,
@@ -375,6 +387,11 @@ double hbls_mad_peak_ops(void);
 /* elapsed device-time of the last batch call on this thread's stream, in ns
  * (HIP events); 0 if unavailable.  For bench.py's roofline leg. */
 uint64_t hbls_last_kernel_ns(void);
+/* host-side intervals (steady clock, ns) of the last aggregate-verify call on
+ * this thread: 0 device allocations, 1 time spent inside upload calls,
+ * 2 first launch to results on the host, 3 frees, 4 the whole call.  Other
+ * indices return 0. */
+uint64_t hbls_last_host_ns(int i);
 
 #ifdef __cplusplus
 }
