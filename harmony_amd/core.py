@@ -136,6 +136,20 @@ def _load():
     lib.hbls_copy_bench_ns.argtypes = [ctypes.c_size_t]
     lib.hbls_fpmul_bench_waves.restype = ctypes.c_double
     lib.hbls_fpmul_bench_waves.argtypes = [ctypes.c_int, ctypes.c_int]
+    # epoch contexts; guarded so that an older library loads
+    if hasattr(lib, "hbls_ctxset_create"):
+        lib.hbls_ctxset_create.restype = ctypes.c_void_p
+        lib.hbls_ctxset_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        lib.hbls_ctxset_free.argtypes = [ctypes.c_void_p]
+        lib.hbls_ctxset_free.restype = None
+        lib.hbls_ctxset_size.argtypes = [ctypes.c_void_p]
+        lib.hbls_ctxset_size.restype = ctypes.c_size_t
+        lib.hbls_batch_seal_verify_ctx.argtypes = [
+            ctypes.c_void_p, u32p, ctypes.c_char_p, u32p, ctypes.c_char_p, u32p,
+            ctypes.c_size_t, ctypes.c_int, i32p]
+        lib.hbls_ctx_mask_sums.argtypes = [
+            ctypes.c_void_p, u32p, ctypes.c_char_p, u32p, ctypes.c_size_t,
+            ctypes.c_char_p, u64p, u32p, i32p]
     return lib
 
 
@@ -171,7 +185,8 @@ def last_kernel_ns() -> int:
 def last_stage_ns(i: int) -> int:
     """device time of stage i of the last aggregate-verify call on this
     thread: 0 mask aggregate, 1 hash-to-G2, 2 decompress, 3 pairing,
-    7 quorum by mask (k_mask_power)"""
+    7 quorum by mask (k_mask_power; for ContextSet.seal_verify the front:
+    prepare and quorum by mask)"""
     return _lib.hbls_last_stage_ns(i)
 
 
@@ -365,6 +380,20 @@ def pack_key_lists(key_lists, batch=None):
     if key_off[-1] >= 1 << 31:
         raise ValueError("too many key indices for one call")
     return key_off, key_idx
+
+
+def pack_blobs(blobs):
+    """Byte strings of any lengths in the CSR form of the epoch-context
+    entries: returns (cat, off) with item j at
+    cat[off[j]:off[j + 1]]; off holds len(blobs) + 1 uint32 values.  Raises
+    BadInputError when the total exceeds 2^32 - 1.  Needs no GPU."""
+    off, total = [0], 0
+    for b in blobs:
+        total += len(b)
+        if total > 0xffffffff:
+            raise BadInputError("pack_blobs: more than 2^32 - 1 bytes in one call")
+        off.append(total)
+    return b"".join(blobs), off
 
 
 def _csr_arrays(key_lists, batch, csr=None):
@@ -570,6 +599,90 @@ class Committee:
         try:
             if getattr(self, "_h", None):
                 _lib.hbls_committee_free(self._h)
+        except Exception:
+            pass
+
+
+class ContextSet:
+    """Device-resident table of epoch contexts: several
+    committees behind one batch call.  Item j of a call names its committee by
+    ctx_idx[j], the position in `committees`.  Each committee's set_quorum, if
+    it is to be used, must have been called before the set is built."""
+
+    def __init__(self, committees):
+        if not hasattr(_lib, "hbls_ctxset_create"):
+            raise HblsError("this libhbls.so has no epoch-context entries: rebuild it")
+        self.committees = list(committees)    # keep alive: the set borrows them
+        n = len(self.committees)
+        arr = (ctypes.c_void_p * max(n, 1))(*[c._h for c in self.committees])
+        self._h = _lib.hbls_ctxset_create(arr, n)
+        if not self._h:
+            if device_count() == 0:
+                raise NoGpuError("ctxset_create: no AMD GPU")
+            raise BadInputError("ctxset_create: empty set or invalid committee")
+
+    def __len__(self):
+        return _lib.hbls_ctxset_size(self._h)
+
+    @staticmethod
+    def _u32(values, what):
+        if any(not 0 <= v <= 0xffffffff for v in values):
+            raise BadInputError(f"{what}: not a uint32")
+        return (ctypes.c_uint32 * max(len(values), 1))(*values)
+
+    def seal_verify(self, ctx_idx, blobs, msgs, quorum=False, offsets=None):
+        """verifySignature over a window that mixes contexts: blobs[j] is the
+        raw commitSigAndBitmap of item j, msgs[j] its payload (any length),
+        ctx_idx[j] its committee.  Per item 1 accept, 0 reject,
+        HBLS_ERR_BADINPUT (context index out of range, or a blob that is not
+        96 + ceil(n/8) bytes of its committee) and, with quorum=True,
+        NOQUORUM.  offsets=(blob_off, msg_off) replaces the offsets computed
+        from the lists (passed on as they are)."""
+        batch = len(ctx_idx)
+        if len(blobs) != batch or len(msgs) != batch:
+            raise ValueError("ctx_idx/blobs/msgs length mismatch")
+        if batch == 0:
+            return []
+        bcat, boff = pack_blobs(blobs)
+        mcat, moff = pack_blobs(msgs)
+        if offsets is not None:
+            boff, moff = offsets
+            if len(boff) != batch + 1 or len(moff) != batch + 1:
+                raise ValueError("offsets must hold batch + 1 entries")
+            if max(boff) > len(bcat) or max(moff) > len(mcat):
+                raise ValueError("offsets point past the data")
+        res = (ctypes.c_int32 * batch)()
+        _check(_lib.hbls_batch_seal_verify_ctx(
+            self._h, self._u32(ctx_idx, "ctx_idx"), bcat, self._u32(boff, "blob_off"),
+            mcat, self._u32(moff, "msg_off"), batch, int(bool(quorum)), res),
+            "batch_seal_verify_ctx")
+        return list(res)
+
+    def mask_sums(self, ctx_idx, bitmaps):
+        """(sums, powers, counts, ok) of bare bitmaps against their contexts:
+        serialized masked key sum (48 zero bytes = infinity), masked voting
+        power, in-range popcount, and 1 / HBLS_ERR_BADINPUT per item (a bad
+        item has a zero block, power 0 and count 0)."""
+        batch = len(ctx_idx)
+        if len(bitmaps) != batch:
+            raise ValueError("ctx_idx/bitmaps length mismatch")
+        if batch == 0:
+            return [], [], [], []
+        cat, off = pack_blobs(bitmaps)
+        out = ctypes.create_string_buffer(48 * batch)
+        pw = (ctypes.c_uint64 * batch)()
+        cn = (ctypes.c_uint32 * batch)()
+        ok = (ctypes.c_int32 * batch)()
+        _check(_lib.hbls_ctx_mask_sums(
+            self._h, self._u32(ctx_idx, "ctx_idx"), cat, self._u32(off, "bm_off"), batch,
+            out, pw, cn, ok), "ctx_mask_sums")
+        return ([out.raw[48 * j:48 * (j + 1)] for j in range(batch)], list(pw), list(cn),
+                list(ok))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _lib.hbls_ctxset_free(self._h)
         except Exception:
             pass
 

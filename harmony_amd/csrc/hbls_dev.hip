@@ -2795,6 +2795,59 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
  * on the device yet */
 struct AggHostSrc { const uint8_t *bitmaps, *sigs, *msgs; };
 
+/* the pairing stage of the aggregate-verify pipeline and its epilogue: the
+ * exact or the combined check over masked key sums, hash points and
+ * decompressed signatures already enqueued on the null stream, then the
+ * stage intervals (ev[2s], ev[2s+1] around stage s; ev[2] is the call's
+ * first event) and the verdicts to the host.  mode_batch is the batch size
+ * the exact/combined rule is applied to.  Shared by run_agg_verify_pipeline
+ * and the epoch-context entry (hbls_ctxset.inc). */
+static int run_agg_verify_pairing(const g1_t *d_agg, g2_t *d_hm, g2aff_t *d_saff,
+                                  int32_t *d_sflags, int32_t *d_hok, int32_t *d_res,
+                                  size_t batch, size_t mode_batch, const EventSet<8> &ev,
+                                  uint64_t t_launch, int32_t *results) {
+    int nb = (int)((batch + 63) / 64);
+    (void)hipEventRecord(ev[6], 0);
+    int arc = AGGRLC_FALLBACK;
+    if (aggrlc_wanted(mode_batch)) {
+        arc = aggrlc_verify(d_agg, d_hm, d_saff, d_sflags, d_hok, d_res, batch);
+        if (arc != HBLS_OK && arc != AGGRLC_FALLBACK) return arc;
+    }
+    if (arc == HBLS_OK) {
+        /* combined path wrote every result */
+    } else if ((int)batch <= coop_threshold()) {
+        LAUNCH_COOP(k_verify_coop, batch, d_agg, d_hm, d_saff, d_sflags, d_hok, d_res,
+                    (int)batch);
+    } else if (rf_mode() == 0 && use_batch_affine()) {
+        DevBuf dpa(batch * sizeof(g1aff_t)), dpi(batch * 4), dha(batch * sizeof(g2aff_t));
+        if (dpa.err || dpi.err || dha.err) return HBLS_ERR;
+        int nba = (int)((batch + 64 * BA_K - 1) / (64 * BA_K));
+        hipLaunchKernelGGL(k_g1_batch_affine, dim3(nba), dim3(64), 0, 0,
+                           d_agg, dpa.as<g1aff_t>(), dpi.as<int32_t>(), (int)batch);
+        hipLaunchKernelGGL(k_g2_batch_affine, dim3(nba), dim3(64), 0, 0,
+                           d_hm, dha.as<g2aff_t>(), d_hok, (int)batch);
+        hipLaunchKernelGGL(k_verify_aff, dim3(nb), dim3(64), 0, 0,
+                           dpa.as<g1aff_t>(), dpi.as<int32_t>(), dha.as<g2aff_t>(),
+                           d_saff, d_sflags, d_hok, d_res, (int)batch);
+        HIP_OK(hipDeviceSynchronize());   /* dpa/dha freed at scope exit */
+    } else {
+        LAUNCH_VERIFY_SCALAR(nb, d_agg, d_hm, d_saff, d_sflags, d_hok, d_res, (int)batch);
+    }
+    (void)hipEventRecord(ev[7], 0);
+    HIP_OK(hipEventSynchronize(ev[7]));
+    float ms_total = 0, ms = 0;
+    (void)hipEventElapsedTime(&ms_total, ev[2], ev[7]);
+    g_last_ns = (uint64_t)(ms_total * 1e6);
+    for (int i = 0; i < 4; i++) {
+        (void)hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]);
+        g_stage_ns[i] = (uint64_t)(ms * 1e6);
+    }
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpy(results, d_res, batch * 4, hipMemcpyDeviceToHost));
+    g_host_ns[2] += host_now_ns() - t_launch;
+    return HBLS_OK;
+}
+
 /* the four-stage aggregate-verify pipeline over DEVICE-resident inputs
  * (bitmaps, serialized sigs, messages) — shared by the host-buffer entry
  * points and the HBM-direct seal-blob path.  Launch order: hash (reads the
@@ -2859,49 +2912,9 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
                                          c->d_wtab, c->d_winf);
     (void)hipEventRecord(ev[1], 0);
 
-    (void)hipEventRecord(ev[6], 0);
-    int arc = AGGRLC_FALLBACK;
-    if (aggrlc_wanted(batch)) {
-        arc = aggrlc_verify(dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
-                            dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), batch);
-        if (arc != HBLS_OK && arc != AGGRLC_FALLBACK) return arc;
-    }
-    if (arc == HBLS_OK) {
-        /* combined path wrote every result */
-    } else if ((int)batch <= coop_threshold()) {
-        int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
-        LAUNCH_COOP(k_verify_coop, batch, dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
-                           dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), (int)batch);
-    } else if (rf_mode() == 0 && use_batch_affine()) {
-        DevBuf dpa(batch * sizeof(g1aff_t)), dpi(batch * 4), dha(batch * sizeof(g2aff_t));
-        if (dpa.err || dpi.err || dha.err) return HBLS_ERR;
-        int nba = (int)((batch + 64 * BA_K - 1) / (64 * BA_K));
-        hipLaunchKernelGGL(k_g1_batch_affine, dim3(nba), dim3(64), 0, 0,
-                           dagg.as<g1_t>(), dpa.as<g1aff_t>(), dpi.as<int32_t>(), (int)batch);
-        hipLaunchKernelGGL(k_g2_batch_affine, dim3(nba), dim3(64), 0, 0,
-                           dhm.as<g2_t>(), dha.as<g2aff_t>(), dhok.as<int32_t>(), (int)batch);
-        hipLaunchKernelGGL(k_verify_aff, dim3(nb), dim3(64), 0, 0,
-                           dpa.as<g1aff_t>(), dpi.as<int32_t>(), dha.as<g2aff_t>(),
-                           dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), dhok.as<int32_t>(),
-                           dres.as<int32_t>(), (int)batch);
-        HIP_OK(hipDeviceSynchronize());   /* dpa/dha freed at scope exit */
-    } else {
-        LAUNCH_VERIFY_SCALAR(nb, dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
-                           dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), (int)batch);
-    }
-    (void)hipEventRecord(ev[7], 0);
-    HIP_OK(hipEventSynchronize(ev[7]));
-    float ms_total = 0, ms = 0;
-    (void)hipEventElapsedTime(&ms_total, ev[2], ev[7]);
-    g_last_ns = (uint64_t)(ms_total * 1e6);
-    for (int i = 0; i < 4; i++) {
-        (void)hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]);
-        g_stage_ns[i] = (uint64_t)(ms * 1e6);
-    }
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpy(results, dres.p, batch * 4, hipMemcpyDeviceToHost));
-    g_host_ns[2] += host_now_ns() - t_launch;
-    return HBLS_OK;
+    return run_agg_verify_pairing(dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
+                                  dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(),
+                                  batch, batch, ev, t_launch, results);
 }
 
 extern "C" int hbls_batch_agg_verify(const hbls_committee_t *c, const uint8_t *bitmaps,
@@ -4274,6 +4287,7 @@ __global__ void k_stream_gather_check(const uint32_t *bitmap, int nwords, int bm
 #include "hbls_rlc.inc"
 #include "hbls_aggrlc.inc"
 #include "hbls_quorum.inc"
+#include "hbls_ctxset.inc"
 #include "hbls_multikey.inc"
 
 extern "C" void hbls_stream_free(hbls_stream *s);

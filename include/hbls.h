@@ -242,6 +242,64 @@ int hbls_batch_seal_verify_quorum(const hbls_committee_t *c,
 int hbls_agg_verify_quorum(const hbls_committee_t *c, const uint8_t *bitmap,
                            const uint8_t sig96[96], const uint8_t *msg, size_t msg_len);
 
+/* ---- epoch contexts: several committees in one batch ----
+ * verifySignature looks up an epoch context — the key list and quorum
+ * verifier of one (shardID, epoch), engine.go:644-659, :720-761 — per item, and
+ * its callers mix contexts in one loop: cross-link lists
+ * (core/blockchain_impl.go:403-424), the epoch chain (core/epochchain.go:125-138)
+ * and a sync window that crosses an epoch boundary
+ * (stagedstreamsync/sig_verify.go:51).  A context set makes that one call. */
+typedef struct hbls_ctxset hbls_ctxset_t;
+
+/* device-resident table of n_ctx committee descriptors.  The committees are
+ * borrowed, not owned: they must outlive the set, and their quorum policy must
+ * be set (if it is to be used) before the set is created.  Immutable after
+ * creation, so it can be shared between threads.  NULL on n_ctx == 0, a NULL
+ * member or allocation failure. */
+hbls_ctxset_t *hbls_ctxset_create(const hbls_committee_t *const *cs, size_t n_ctx);
+void   hbls_ctxset_free(hbls_ctxset_t *s);
+size_t hbls_ctxset_size(const hbls_ctxset_t *s);
+
+/* verifySignature (engine.go:619-642) for a window that mixes epoch contexts.
+ * Item j is the raw commitSigAndBitmap blob  blobs[blob_off[j] .. blob_off[j+1])
+ * checked against committee ctx_idx[j] on message msgs[msg_off[j] .. msg_off[j+1]).
+ * blob_off and msg_off have batch+1 entries, start at 0 and never decrease
+ * (else the call fails with HBLS_ERR_BADINPUT before any upload, as the CSR
+ * arguments of the multi-key entries do).
+ * results[j] is what hbls_batch_seal_verify (quorum != 0:
+ * hbls_batch_seal_verify_quorum) returns for item j alone against
+ * cs[ctx_idx[j]], in both verify modes; the exact/combined rule of
+ * hbls_set_agg_verify_mode is applied to the size of the whole batch, and
+ * chunks of the combined mode are formed over the mixed batch.
+ * An item with ctx_idx[j] >= n_ctx, or whose blob is not 96 + ceil(n/8) bytes
+ * of its context (ParseCommitSigAndBitmap, internal/chain/sig.go:23;
+ * Mask.SetMask, crypto/bls/mask.go:114-120), gets HBLS_ERR_BADINPUT as its
+ * own code, decided on the device before the index or the length is used as
+ * an address; the other items keep their verdicts.
+ * A message may have any length: the result is that of hbls_hash_to_g2 on
+ * those bytes (which reads the first min(len, 48) bytes, zero-padded).
+ * quorum != 0 runs IsQuorumAchievedByMask first, as the *_quorum entries do:
+ * malformed -> HBLS_ERR_BADINPUT, then no quorum -> HBLS_NOQUORUM, then the
+ * pairing, with the ordering difference noted at hbls_batch_agg_verify_quorum;
+ * the call then fails with HBLS_ERR_BADINPUT if any committee of the set has
+ * no policy set.  Malformed and quorumless items take no part in hash-to-G2,
+ * decompression or pairing. */
+int hbls_batch_seal_verify_ctx(const hbls_ctxset_t *s, const uint32_t *ctx_idx,
+                               const uint8_t *blobs, const uint32_t *blob_off,
+                               const uint8_t *msgs,  const uint32_t *msg_off,
+                               size_t batch, int quorum, int32_t *results);
+
+/* the front half alone, for parity tests and for callers that only need the
+ * tally: per item the serialized masked key sum (48 zero bytes = infinity, as
+ * hbls_mask_aggregate_g1), masked power and in-range popcount; ok[j] = 1 or
+ * HBLS_ERR_BADINPUT (bad context index or a row that is not ceil(n/8) bytes:
+ * zero block, power 0, count 0).  Items are bare bitmaps in CSR form.  Any
+ * output but ok may be NULL. */
+int hbls_ctx_mask_sums(const hbls_ctxset_t *s, const uint32_t *ctx_idx,
+                       const uint8_t *bitmaps, const uint32_t *bm_off, size_t batch,
+                       uint8_t *out48s, uint64_t *power_out, uint32_t *count_out,
+                       int32_t *ok);
+
 /* AggregateSig batch form (crypto/bls/mask.go:57-64): out = sum of n sigs */
 int hbls_g2_aggregate(const uint8_t *sigs96, size_t n, uint8_t out96[96]);
 
