@@ -136,6 +136,14 @@ def _load():
     lib.hbls_copy_bench_ns.argtypes = [ctypes.c_size_t]
     lib.hbls_fpmul_bench_waves.restype = ctypes.c_double
     lib.hbls_fpmul_bench_waves.argtypes = [ctypes.c_int, ctypes.c_int]
+    # test hooks (not in include/hbls.h): device self-tests and the
+    # operation-level arithmetic probe
+    lib.hbls_coop_selftest.restype = ctypes.c_int
+    lib.hbls_fpmul_asm_check.restype = ctypes.c_longlong
+    lib.hbls_arith_probe.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
+                                     ctypes.c_char_p, i32p]
+    lib.hbls_arith_probe_op_name.argtypes = [ctypes.c_int]
+    lib.hbls_arith_probe_op_name.restype = ctypes.c_char_p
     # epoch contexts; guarded so that an older library loads
     if hasattr(lib, "hbls_ctxset_create"):
         lib.hbls_ctxset_create.restype = ctypes.c_void_p
@@ -342,6 +350,43 @@ def batch_keccak256(msgs: bytes, mlen: int, batch: int) -> bytes:
     out = ctypes.create_string_buffer(32 * batch)
     _check(_lib.hbls_batch_keccak256(msgs, mlen, batch, out), "batch_keccak")
     return out.raw
+
+
+COOP_SELFTEST_STAGES = ("fp12_mul", "fp12_sqr", "mul_line", "cyc_sqr", "dbl_step",
+                        "add_step", "pow_u", "final_exp")
+
+
+def coop_selftest() -> int:
+    """k_coop_selftest: every cooperative building block against its scalar
+    twin on the device.  0 = all equal; bit i set = stage i of
+    COOP_SELFTEST_STAGES differs; negative = the launch failed."""
+    return _lib.hbls_coop_selftest()
+
+
+def coop_selftest_failed_stages(mask: int):
+    return [s for i, s in enumerate(COOP_SELFTEST_STAGES) if mask >> i & 1]
+
+
+def fpmul_asm_check() -> int:
+    """mismatches between the generated asm CIOS core and the C body over
+    dependent chains of random operands; 0 = bit-exact, -1 = launch failed"""
+    return _lib.hbls_fpmul_asm_check()
+
+
+def arith_probe_ops():
+    """names of the probe's operations, by operation number"""
+    return [_lib.hbls_arith_probe_op_name(i).decode()
+            for i in range(_lib.hbls_arith_probe_op_count())]
+
+
+def arith_probe(op: int, data: bytes, n_items: int, out_fp: int):
+    """Test hook: run operation `op` on n_items operand sets
+    of raw device-domain limbs.  Returns (out bytes, n_items x out_fp x 48;
+    flags, one int per item)."""
+    out = ctypes.create_string_buffer(max(1, n_items * out_fp * 48))
+    flags = (ctypes.c_int32 * max(1, n_items))()
+    _check(_lib.hbls_arith_probe(op, data, n_items, out, flags), "arith_probe")
+    return out.raw[:n_items * out_fp * 48], list(flags)[:n_items]
 
 
 def construct_commit_payload(block_num: int, hash32: bytes, view_id: int,
