@@ -119,6 +119,9 @@ def _load():
     lib.hbls_aggrlc_last_stats.restype = None
     lib.hbls_set_aggrlc_final.argtypes = [ctypes.c_int]
     lib.hbls_aggrlc_final_selftest.argtypes = [ctypes.c_int]
+    lib.hbls_set_aggrlc_sigleg.argtypes = [ctypes.c_int]
+    lib.hbls_aggrlc_probe.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
+                                      ctypes.c_char_p]
     lib.hbls_last_host_ns.restype = ctypes.c_uint64
     lib.hbls_last_host_ns.argtypes = [ctypes.c_int]
     u64p, u32p, i32p = (ctypes.POINTER(t) for t in
@@ -194,7 +197,8 @@ def last_stage_ns(i: int) -> int:
     """device time of stage i of the last aggregate-verify call on this
     thread: 0 mask aggregate, 1 hash-to-G2, 2 decompress, 3 pairing,
     7 quorum by mask (k_mask_power; for ContextSet.seal_verify the front:
-    prepare and quorum by mask)"""
+    prepare and quorum by mask); in the plain entries 7 is the combined
+    path's signature scaling and chunk sums"""
     return _lib.hbls_last_stage_ns(i)
 
 
@@ -258,6 +262,30 @@ def aggrlc_final_selftest(nchunks: int) -> int:
     """chunks on which the cooperative final kernels and the one-lane kernel
     disagree over nchunks deterministic chunk products (0 = parity)"""
     return _check(_lib.hbls_aggrlc_final_selftest(nchunks), "aggrlc_final_selftest")
+
+
+def set_aggrlc_sigleg(leg: int):
+    """where the combined path pairs the signatures: 0 = one
+    Miller leg per item, 1 = one per chunk on the chunk's scaled signature
+    sum, -1 = the default rule.  Verdicts and stats do not depend on it."""
+    _check(_lib.hbls_set_aggrlc_sigleg(leg), "set_aggrlc_sigleg")
+
+
+AGGRLC_PROBE_OPS = {"g1_mul64w": (0, 3 * 48 + 8, 3 * 48),
+                    "g2_mul64w": (1, 6 * 48 + 8, 6 * 48),
+                    "miller1_fe": (2, 6 * 48, 12 * 48)}
+
+
+def aggrlc_probe(name: str, data: bytes, n_items: int) -> bytes:
+    """Test hook: run g1_mul64w / g2_mul64w (Jacobian point
+    and a little-endian u64 scalar per item) or miller1_fe (affine Q, affine
+    P) on raw device-domain limbs; returns the raw results."""
+    op, in_b, out_b = AGGRLC_PROBE_OPS[name]
+    if len(data) != n_items * in_b:
+        raise ValueError("aggrlc_probe: operand size")
+    out = ctypes.create_string_buffer(max(1, n_items * out_b))
+    _check(_lib.hbls_aggrlc_probe(op, data, n_items, out), "aggrlc_probe")
+    return out.raw[:n_items * out_b]
 
 
 def last_host_ns(i: int) -> int:

@@ -21,6 +21,109 @@
 #define AGGRLC_CHUNK 64         /* items per product == threads per block */
 #define AGGRLC_WINDOWS 8        /* 8-bit windows of a 64-bit scalar */
 
+/* ---- the signature leg once per chunk (DESIGN.md §4k).  The pairing is
+ * bilinear, so after the final exponentiation the signature factors of a
+ * chunk multiply to e(-G1, S_c) with S_c = sum_i r_i*sig_i: one Miller leg on
+ * S_c per chunk replaces one per item.  The group element checked is the
+ * same as above, so is the soundness argument.  Each item pays a 64-bit G2
+ * scalar multiplication (k_aggrlc_sigscale) and a G2 addition in a tree
+ * (k_aggrlc_sigsum) instead; its own Miller loop keeps one leg. */
+
+/* signed 4-bit digits of a 64-bit scalar: k = sum_j d_j 16^j, j = 0..16,
+ * -8 <= d_j <= 8.  mag holds |d_0|..|d_15| as nibbles, neg their signs as
+ * bits, top is d_16 (0 or 1: the carry out of the last window).  A window
+ * value above 8 becomes value-16 with a carry; exactly 8 goes to -8 with a
+ * carry when the next window carries anyway (its nibble is 8 or more) and
+ * stays +8 otherwise. */
+DEV void aggrlc_recode64(uint64_t k, uint64_t &mag, uint32_t &neg, uint32_t &top) {
+    uint32_t c = 0;
+    mag = 0; neg = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        uint32_t v = ((uint32_t)(k >> (4 * j)) & 15u) + c;
+        uint32_t nx = j < 15 ? ((uint32_t)(k >> (4 * j + 4)) & 15u) : 0u;
+        c = (v > 8u || (v == 8u && nx >= 8u)) ? 1u : 0u;
+        uint32_t m = c ? 16u - v : v;
+        mag |= (uint64_t)m << (4 * j);
+        neg |= (c && m) ? (1u << j) : 0u;
+    }
+    top = c;
+}
+
+/* r = k*p for a 64-bit k, fixed 4-bit signed windows over a per-lane table
+ * of 1p..8p: 64 doublings and at most 16 additions after the table's 4 + 3,
+ * with control flow that depends on the scalar only through the "digit is
+ * zero" skip — a wave of 64 independent scalars runs g1_mul's 63 additions,
+ * here 16.  The same group element as g1_mul for every k, p = identity
+ * included (g1_add and g1_dbl carry the identity and the doubling case). */
+DEVN void g1_mul64w(g1_t &r, const g1_t &p, uint64_t k) {
+    g1_t tab[8];
+    tab[0] = p;
+    g1_dbl(tab[1], tab[0]);
+    g1_add(tab[2], tab[1], tab[0]);
+    g1_dbl(tab[3], tab[1]);
+    g1_add(tab[4], tab[3], tab[0]);
+    g1_dbl(tab[5], tab[2]);
+    g1_add(tab[6], tab[5], tab[0]);
+    g1_dbl(tab[7], tab[3]);
+    uint64_t mag; uint32_t neg, top;
+    aggrlc_recode64(k, mag, neg, top);
+    g1_t acc;
+    if (top) acc = p; else g1_set_inf(acc);
+    for (int j = 15; j >= 0; j--) {
+        for (int s = 0; s < 4; s++) g1_dbl(acc, acc);
+        uint32_t m = (uint32_t)(mag >> (4 * j)) & 15u;
+        if (m) {
+            g1_t t = tab[m - 1];
+            if ((neg >> j) & 1u) fp_neg(t.y, t.y);
+            g1_add(acc, acc, t);
+        }
+    }
+    r = acc;
+}
+DEVN void g2_mul64w(g2_t &r, const g2_t &p, uint64_t k) {
+    g2_t tab[8];
+    tab[0] = p;
+    g2_dbl(tab[1], tab[0]);
+    g2_add(tab[2], tab[1], tab[0]);
+    g2_dbl(tab[3], tab[1]);
+    g2_add(tab[4], tab[3], tab[0]);
+    g2_dbl(tab[5], tab[2]);
+    g2_add(tab[6], tab[5], tab[0]);
+    g2_dbl(tab[7], tab[3]);
+    uint64_t mag; uint32_t neg, top;
+    aggrlc_recode64(k, mag, neg, top);
+    g2_t acc;
+    if (top) acc = p; else g2_set_inf(acc);
+    for (int j = 15; j >= 0; j--) {
+        for (int s = 0; s < 4; s++) g2_dbl(acc, acc);
+        uint32_t m = (uint32_t)(mag >> (4 * j)) & 15u;
+        if (m) {
+            g2_t t = tab[m - 1];
+            if ((neg >> j) & 1u) fp2_neg(t.y, t.y);
+            g2_add(acc, acc, t);
+        }
+    }
+    r = acc;
+}
+
+/* f = f_{|z|,Q}(P): one leg of miller_loop2, the same homogeneous steps */
+DEVN void miller_loop1_h(fp12_t &f, const g2aff_t &Q, const g1aff_t &P) {
+    g2_t T;
+    g2_from_affine(T, Q);
+    fp2_t c0, c3, c5;
+    fp12_one(f);
+    for (int bit = 62; bit >= 0; bit--) {
+        fp12_sqr(f, f);
+        ml_dbl_step_h(T, P, c0, c3, c5);
+        fp12_mul_line(f, c0, c3, c5);
+        if ((BLS_U >> bit) & 1) {
+            ml_add_step_h(T, Q, P, c0, c3, c5);
+            fp12_mul_line(f, c0, c3, c5);
+        }
+    }
+}
+
 /* p2[k] = 2^k * (-G1), affine (thread k: k doublings, one inversion): the
  * 64 "keys" whose 8-key subset sums (k_wtab_build_jac) are the fixed-base
  * window table of -G1 */
@@ -62,7 +165,7 @@ __global__ void k_aggrlc_miller(const g1_t *aggpubs, const g2_t *hms, const g2af
     uint64_t r = scalars[i];
     if (r == 0) r = 1;
     g1_t A, C;
-    g1_mul(A, aggpubs[i], &r, 1);
+    g1_mul64w(A, aggpubs[i], r);
     g1_set_inf(C);
     for (int w = 0; w < AGGRLC_WINDOWS; w++) {
         uint32_t b = (uint32_t)(r >> (8 * w)) & 255u;
@@ -94,12 +197,127 @@ __global__ void k_aggrlc_miller(const g1_t *aggpubs, const g2_t *hms, const g2af
     results[i] = 1;      /* stands unless the chunk fails and is re-checked */
 }
 
+/* chunk-level signature leg, step 1 — thread per item: k_aggrlc_miller's
+ * classification in its guard order (aggpubs[i] is read for g1_is_inf only),
+ * then B_i = r_i*sig_i, Jacobian.  Classified items get elig 0 and B_i =
+ * identity, so the chunk sum needs no flags. */
+__global__ void k_aggrlc_sigscale(const g1_t *aggpubs, const g2aff_t *sigs,
+                                  const int32_t *sig_flags, const int32_t *hm_ok,
+                                  const uint64_t *scalars, g2_t *B, int32_t *elig,
+                                  int32_t *results, int batch) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch) return;
+    g2_t b;
+    g2_set_inf(b);
+    elig[i] = 0;
+    if (!hm_ok[i] || sig_flags[i] == 0) {
+        results[i] = HBLS_ERR_BADINPUT; B[i] = b; return;
+    }
+    bool sig_inf = sig_flags[i] == 2;
+    bool pub_inf = g1_is_inf(aggpubs[i]);
+    if (pub_inf || sig_inf) {
+        results[i] = (pub_inf && sig_inf) ? 1 : 0;   /* herumi edge */
+        B[i] = b; return;
+    }
+    uint64_t r = scalars[i];
+    if (r == 0) r = 1;
+    g2_t s;
+    g2_from_affine(s, sigs[i]);
+    g2_mul64w(b, s, r);
+    B[i] = b;
+    elig[i] = 1;
+    results[i] = 1;      /* stands unless the chunk fails and is re-checked */
+}
+
+/* step 2 — one block per chunk (k_rlc_chunk_sum's shape): LDS tree over the
+ * chunk's B_i, then lane 0 stores S_c affine.  sflag[c]: 1 = S[c] is an
+ * affine point, 0 = the sum is the identity (no eligible item, or signatures
+ * that cancel): its pairing value is one and the chunk entry contributes one;
+ * the chunk's verdict still comes from the items' own factors. */
+__global__ void __launch_bounds__(AGGRLC_CHUNK) k_aggrlc_sigsum(
+        const g2_t *B, int batch, int nchunks, g2aff_t *S, int32_t *sflag) {
+    int c = blockIdx.x;
+    if (c >= nchunks) return;
+    __shared__ g2_t red[AGGRLC_CHUNK];
+    size_t i = (size_t)c * AGGRLC_CHUNK + threadIdx.x;
+    if (i < (size_t)batch) red[threadIdx.x] = B[i];
+    else g2_set_inf(red[threadIdx.x]);
+    __syncthreads();
+    for (int s = AGGRLC_CHUNK / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+            g2_t t;
+            g2_add(t, red[threadIdx.x], red[threadIdx.x + s]);
+            red[threadIdx.x] = t;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        g2_t sum = red[0];
+        if (g2_is_inf(sum)) {
+            sflag[c] = 0;
+        } else {
+            g2aff_t a;
+            g2_to_affine(a, sum);
+            S[c] = a;
+            sflag[c] = 1;
+        }
+    }
+}
+
+/* step 3 — batch + nchunks threads, one Miller leg each.  Thread i < batch
+ * with elig 1: f(H_i; r_i*aggpk_i), or elig 2 when the scaled key sum is the
+ * identity (as k_aggrlc_miller).  Thread batch + c: the chunk entry
+ * f(S_c; -G1), one when sflag[c] is 0.  Both kinds meet in one call of the
+ * loop, so the block that holds the boundary does not run it twice. */
+__global__ void k_aggrlc_miller1(const g1_t *aggpubs, const g2_t *hms,
+                                 const uint64_t *scalars, const g2aff_t *S,
+                                 const int32_t *sflag, fp12_t *F, int32_t *elig,
+                                 int32_t *results, int batch, int nchunks) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)batch + (size_t)nchunks) return;
+    fp12_t f;
+    g2aff_t Q;
+    g1aff_t P;
+    bool run = false;
+    if (i < (size_t)batch) {
+        if (elig[i] == 1) {
+            uint64_t r = scalars[i];
+            if (r == 0) r = 1;
+            g1_t A;
+            g1_mul64w(A, aggpubs[i], r);
+            if (g1_is_inf(A)) {
+                elig[i] = 2; results[i] = 0;
+            } else {
+                g1_to_affine(P, A);
+                g2_t hmc = hms[i];
+                g2_to_affine(Q, hmc);
+                run = true;
+            }
+        }
+    } else {
+        size_t c = i - (size_t)batch;
+        if (sflag[c]) {
+            Q = S[c];
+            fp_load(P.x, BLS_G1_X);
+            fp_t gy;
+            fp_load(gy, BLS_G1_Y);
+            fp_neg(P.y, gy);
+            run = true;
+        }
+    }
+    if (run) miller_loop1_h(f, Q, P);
+    else fp12_one(f);
+    F[i] = f;
+}
+
 /* one block per chunk: LDS tree product of the chunk's eligible f values
  * (the ragged tail and the classified items contribute one).  ccnt[c] =
- * eligible items, cforce[c] = some item asked for the exact path. */
+ * eligible items, cforce[c] = some item asked for the exact path.  FX, when
+ * given, holds the chunks' own entries (the chunk-level signature leg), which
+ * lane 0 multiplies in after the tree. */
 __global__ void __launch_bounds__(AGGRLC_CHUNK) k_aggrlc_chunk_prod(
         const fp12_t *F, const int32_t *elig, int batch, int nchunks,
-        fp12_t *FC, int32_t *ccnt, int32_t *cforce) {
+        fp12_t *FC, int32_t *ccnt, int32_t *cforce, const fp12_t *FX) {
     int c = blockIdx.x;
     if (c >= nchunks) return;
     __shared__ fp12_t red[AGGRLC_CHUNK];
@@ -118,7 +336,13 @@ __global__ void __launch_bounds__(AGGRLC_CHUNK) k_aggrlc_chunk_prod(
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        FC[c] = red[0];
+        if (FX) {
+            fp12_t t;
+            fp12_mul(t, red[0], FX[c]);
+            FC[c] = t;
+        } else {
+            FC[c] = red[0];
+        }
         ccnt[c] = cnt;
         cforce[c] = force ? 1 : 0;
     }
@@ -250,6 +474,28 @@ extern "C" int hbls_set_aggrlc_final(int kernel) {
     g_aggrlc_final = kernel;
     return HBLS_OK;
 }
+/* where the signature leg is paired: 0 = per item (k_aggrlc_miller, two
+ * legs), 1 = once per chunk (k_aggrlc_sigscale, k_aggrlc_sigsum,
+ * k_aggrlc_miller1).  The default rule is §4e's threshold rule on the
+ * per-call sweep of DESIGN.md §4k: leg 1 from the smallest measured batch at
+ * which it wins the wall clock at every larger one. */
+#define AGGRLC_SIGLEG_MIN_BATCH 16384
+static int g_aggrlc_sigleg = -2;        /* -2: read env on first use; -1: the rule */
+static int aggrlc_sigleg(size_t batch) {
+    if (g_aggrlc_sigleg == -2) {
+        const char *e = getenv("HBLS_AGGRLC_SIGLEG");
+        int k = e ? atoi(e) : -1;
+        g_aggrlc_sigleg = (k == 0 || k == 1) ? k : -1;
+    }
+    if (g_aggrlc_sigleg >= 0) return g_aggrlc_sigleg;
+    return batch >= AGGRLC_SIGLEG_MIN_BATCH ? 1 : 0;
+}
+extern "C" int hbls_set_aggrlc_sigleg(int leg) {
+    if (leg < -1 || leg > 1) return HBLS_ERR_BADINPUT;
+    g_aggrlc_sigleg = leg;
+    return HBLS_OK;
+}
+
 static void launch_aggrlc_final(int kernel, const fp12_t *d_FC, const int32_t *d_ccnt,
                                 const int32_t *d_cforce, int32_t *d_verdict, int nc) {
     if (kernel == 16)
@@ -381,23 +627,37 @@ static bool aggrlc_wanted(size_t batch) {
 /* the verify stage of run_agg_verify_pipeline on the combined path; inputs
  * as k_verify's.  Returns HBLS_OK with d_res complete, AGGRLC_FALLBACK when
  * randomness or memory for the combination is unavailable, HBLS_ERR on a
- * device error.  g_stage_ns[4..6] = Miller, products, final exponentiation. */
+ * device error.  g_stage_ns[4..6] = Miller, products, final exponentiation;
+ * g_stage_ns[7] = the signature scaling and chunk sums of the chunk-level
+ * leg (zero with the per-item leg).  Every launch lies between the caller's
+ * verify-stage events. */
 static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_saff,
                          const int32_t *d_sflags, const int32_t *d_hok,
                          int32_t *d_res, size_t batch) {
     size_t nc = (batch + AGGRLC_CHUNK - 1) / AGGRLC_CHUNK;
+    const int leg = aggrlc_sigleg(batch);
+    const size_t nx = leg ? nc : 0;     /* chunk entries behind the items' f */
     std::vector<uint64_t> scalars(batch);
     if (!rlc_draw_scalars(scalars.data(), batch)) return AGGRLC_FALLBACK;
     FreeClock fclk;
     uint64_t t_alloc = host_now_ns();
-    DevBuf dsc(batch * 8), dF(batch * sizeof(fp12_t)), delig(batch * 4);
-    DevBuf dFC(nc * sizeof(fp12_t)), dcs(3 * nc * 4);
+    /* dF: the items' f, then the chunk entries, then (chunk-level leg) the
+     * scaled signatures B and the chunk sums S — one allocation, so the
+     * per-item leg allocates what it always did; dcs: ccnt | cforce |
+     * verdict | sflag */
+    const size_t f_bytes = (batch + nx) * sizeof(fp12_t);
+    const size_t b_bytes = leg ? batch * sizeof(g2_t) : 0;
+    DevBuf dsc(batch * 8), dF(f_bytes + b_bytes + nx * sizeof(g2aff_t)), delig(batch * 4);
+    DevBuf dFC(nc * sizeof(fp12_t)), dcs((3 * nc + nx) * 4);
     g_host_ns[0] += host_now_ns() - t_alloc;
     FreeClockArm farm(fclk);
     if (dsc.err || dF.err || delig.err || dFC.err || dcs.err) {
         (void)hipGetLastError();
         return AGGRLC_FALLBACK;
     }
+    fp12_t *d_F = dF.as<fp12_t>();
+    g2_t *d_B = (g2_t *)((uint8_t *)dF.p + f_bytes);
+    g2aff_t *d_S = (g2aff_t *)((uint8_t *)dF.p + f_bytes + b_bytes);
     /* the scalars go up beside the kernels already queued, not behind them;
      * `scalars` outlives the copy (the verdict download below waits for the
      * Miller kernel, which waits for the upload) */
@@ -405,29 +665,44 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
     if (up.err != hipSuccess) return HBLS_ERR;
     HIP_OK(upload_then_wait(dsc.p, scalars.data(), batch * 8, up[0]));
     int32_t *d_ccnt = dcs.as<int32_t>(), *d_cforce = d_ccnt + nc, *d_verdict = d_cforce + nc;
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; i++) (void)hipEventCreate(&ev[i]);
+    int32_t *d_sf = d_verdict + nc;
+    /* ev[0..1] around the signature scaling and sums, ev[1..4] as before */
+    EventSet<5> ev;
+    if (ev.err != hipSuccess) return HBLS_ERR;
     (void)hipEventRecord(ev[0], 0);
-    hipLaunchKernelGGL(k_aggrlc_miller, dim3((uint32_t)((batch + 63) / 64)), dim3(64), 0, 0,
-                       d_agg, d_hm, d_saff, d_sflags, d_hok, dsc.as<uint64_t>(),
-                       g_aggrlc_gtab, dF.as<fp12_t>(), delig.as<int32_t>(), d_res, (int)batch);
+    if (leg) {
+        hipLaunchKernelGGL(k_aggrlc_sigscale, dim3((uint32_t)((batch + 63) / 64)), dim3(64), 0, 0,
+                           d_agg, d_saff, d_sflags, d_hok, dsc.as<uint64_t>(), d_B,
+                           delig.as<int32_t>(), d_res, (int)batch);
+        hipLaunchKernelGGL(k_aggrlc_sigsum, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
+                           d_B, (int)batch, (int)nc, d_S, d_sf);
+    }
     (void)hipEventRecord(ev[1], 0);
-    hipLaunchKernelGGL(k_aggrlc_chunk_prod, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
-                       dF.as<fp12_t>(), delig.as<int32_t>(), (int)batch, (int)nc,
-                       dFC.as<fp12_t>(), d_ccnt, d_cforce);
+    if (leg)
+        hipLaunchKernelGGL(k_aggrlc_miller1, dim3((uint32_t)((batch + nc + 63) / 64)), dim3(64),
+                           0, 0, d_agg, d_hm, dsc.as<uint64_t>(), d_S, d_sf, d_F,
+                           delig.as<int32_t>(), d_res, (int)batch, (int)nc);
+    else
+        hipLaunchKernelGGL(k_aggrlc_miller, dim3((uint32_t)((batch + 63) / 64)), dim3(64), 0, 0,
+                           d_agg, d_hm, d_saff, d_sflags, d_hok, dsc.as<uint64_t>(),
+                           g_aggrlc_gtab, d_F, delig.as<int32_t>(), d_res, (int)batch);
     (void)hipEventRecord(ev[2], 0);
+    hipLaunchKernelGGL(k_aggrlc_chunk_prod, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
+                       d_F, delig.as<int32_t>(), (int)batch, (int)nc,
+                       dFC.as<fp12_t>(), d_ccnt, d_cforce,
+                       leg ? d_F + batch : (const fp12_t *)nullptr);
+    (void)hipEventRecord(ev[3], 0);
     launch_aggrlc_final(aggrlc_final_kernel(), dFC.as<fp12_t>(), d_ccnt, d_cforce,
                         d_verdict, (int)nc);
-    (void)hipEventRecord(ev[3], 0);
+    (void)hipEventRecord(ev[4], 0);
     std::vector<int32_t> hc(3 * nc);
     hipError_t e = hipMemcpy(hc.data(), dcs.p, 3 * nc * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipGetLastError();
-    for (int i = 0; i < 3; i++) {
+    for (int i = 0; i < 4; i++) {
         float ms = 0;
-        if (e == hipSuccess) (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-        g_stage_ns[4 + i] = (uint64_t)(ms * 1e6);
+        if (e == hipSuccess && (i || leg)) (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
+        g_stage_ns[i ? 3 + i : 7] = (uint64_t)(ms * 1e6);
     }
-    for (int i = 0; i < 4; i++) (void)hipEventDestroy(ev[i]);
     HIP_OK(e);
 
     std::vector<uint32_t> failed;
@@ -459,5 +734,63 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
                        dsel.as<uint32_t>(), (int)ns, d_agg, d_hm, d_saff, d_sflags, d_hok,
                        d_res, (int)batch);
     HIP_OK(hipGetLastError());
+    return HBLS_OK;
+}
+
+/* ---- test hook for the functions above (not part of the ABI, kept out of
+ * include/hbls.h; raw device-domain limbs as hbls_arith_probe, DESIGN.md §4j,
+ * whose operation table is pinned by its own test and stays as it is).
+ * Item layouts, fp = 48 B:
+ *   0 g1_mul64w   in Jacobian point (3 fp) | u64 scalar   out Jacobian (3 fp)
+ *   1 g2_mul64w   in Jacobian point (6 fp) | u64 scalar   out Jacobian (6 fp)
+ *   2 miller1_fe  in affine Q (4 fp) | affine P (2 fp)    out fp12 (12 fp):
+ *                 final_exp(conj(miller_loop1_h(Q, P))), what the final
+ *                 kernels apply to a chunk product */
+enum { AGGRLC_PROBE_G1_MUL64W = 0, AGGRLC_PROBE_G2_MUL64W = 1, AGGRLC_PROBE_MILLER1_FE = 2,
+       AGGRLC_PROBE_N_OPS = 3 };
+#define AGGRLC_PROBE_MAX_ITEMS 4096
+__global__ void k_aggrlc_probe(int op, const uint64_t *in, int in_w, uint64_t *out, int out_w,
+                               int n) {
+    int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t *src = in + (size_t)j * in_w;
+    uint64_t *dst = out + (size_t)j * out_w;
+    union { uint64_t w[72]; g1_t g1; g2_t g2; g2aff_t q; fp12_t f; } a, o;
+    for (int i = 0; i < in_w && i < 72; i++) a.w[i] = src[i];
+    if (op == AGGRLC_PROBE_G1_MUL64W) {
+        g1_mul64w(o.g1, a.g1, src[18]);
+    } else if (op == AGGRLC_PROBE_G2_MUL64W) {
+        g2_mul64w(o.g2, a.g2, src[36]);
+    } else {
+        g1aff_t p;
+        for (int k = 0; k < 6; k++) { p.x.l[k] = src[24 + k]; p.y.l[k] = src[30 + k]; }
+        fp12_t f;
+        miller_loop1_h(f, a.q, p);
+        fp12_conj(f, f);
+        final_exp(o.f, f);
+    }
+    for (int i = 0; i < out_w; i++) dst[i] = o.w[i];
+}
+static bool probe_limbs_lt_p(const uint8_t *b);     /* hbls_probe.inc */
+extern "C" int hbls_aggrlc_probe(int op, const uint8_t *in, size_t n_items, uint8_t *out) {
+    if (op < 0 || op >= AGGRLC_PROBE_N_OPS) return HBLS_ERR_BADINPUT;
+    if (!in || !out || n_items == 0 || n_items > AGGRLC_PROBE_MAX_ITEMS)
+        return HBLS_ERR_BADINPUT;
+    const int n_fp = op == AGGRLC_PROBE_G1_MUL64W ? 3 : 6;       /* fp elements in */
+    const int in_w = n_fp * 6 + (op == AGGRLC_PROBE_MILLER1_FE ? 0 : 1);
+    const int out_w = op == AGGRLC_PROBE_G1_MUL64W ? 18 : op == AGGRLC_PROBE_G2_MUL64W ? 36 : 72;
+    for (size_t j = 0; j < n_items; j++)
+        for (int i = 0; i < n_fp; i++)
+            if (!probe_limbs_lt_p(in + j * (size_t)in_w * 8 + 48 * i)) return HBLS_ERR_BADINPUT;
+    int rc = require_gpu();
+    if (rc != HBLS_OK) return rc;
+    DevBuf din(n_items * in_w * 8), dout(n_items * out_w * 8);
+    if (din.err || dout.err) return HBLS_ERR;
+    HIP_OK(hipMemcpy(din.p, in, n_items * in_w * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_aggrlc_probe, dim3((uint32_t)((n_items + 63) / 64)), dim3(64), 0, 0,
+                       op, din.as<uint64_t>(), in_w, dout.as<uint64_t>(), out_w, (int)n_items);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(out, dout.p, n_items * out_w * 8, hipMemcpyDeviceToHost));
     return HBLS_OK;
 }

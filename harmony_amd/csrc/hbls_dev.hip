@@ -2874,7 +2874,7 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
         return HBLS_ERR;
     int nb = (int)((batch + 63) / 64);
     aggrlc_stats_reset();
-    for (int i = 4; i < 7; i++) g_stage_ns[i] = 0;    /* the combined path's own, if it runs */
+    for (int i = 4; i < 8; i++) g_stage_ns[i] = 0;    /* the combined path's own, if it runs */
     /* ev[2s], ev[2s+1] around stage s (0 mask, 1 hash, 2 decompress, 3 verify) */
     EventSet<8> ev;
     EventSet<3> up;

@@ -272,8 +272,13 @@ static int run_agg_verify_quorum(const hbls_committee_t *c, const uint8_t *d_bm,
     g_stage_ns[7] = mask_ns;
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(&nlive, dnlive.p, 4, hipMemcpyDeviceToHost));
-    if (nlive == batch)
-        return run_agg_verify_pipeline(c, d_bm, d_sig, d_msg, msg_len, batch, results);
+    if (nlive == batch) {
+        /* the pipeline resets slot 7 (the combined path's own use of it);
+         * in this entry it stays k_mask_power's time */
+        int prc = run_agg_verify_pipeline(c, d_bm, d_sig, d_msg, msg_len, batch, results);
+        g_stage_ns[7] = mask_ns;
+        return prc;
+    }
     std::vector<int32_t> live(batch);
     HIP_OK(hipMemcpy(live.data(), dlive.p, batch * 4, hipMemcpyDeviceToHost));
     if (nlive == 0) {
@@ -299,6 +304,7 @@ static int run_agg_verify_quorum(const hbls_committee_t *c, const uint8_t *d_bm,
     std::vector<int32_t> sub(nlive);
     int rc = run_agg_verify_pipeline(c, gbm.as<uint8_t>(), gsig.as<uint8_t>(),
                                      gmsg.as<uint8_t>(), msg_len, nlive, sub.data());
+    g_stage_ns[7] = mask_ns;
     if (rc != HBLS_OK) return rc;
     size_t k = 0;
     for (size_t j = 0; j < batch; j++) results[j] = live[j] ? sub[k++] : HBLS_NOQUORUM;

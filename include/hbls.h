@@ -432,6 +432,15 @@ int hbls_set_aggrlc_final(int kernel);
  * disagree (0 = parity); HBLS_ERR if the one-lane verdicts are not the ones
  * the inputs dictate, a mix of 0 and 1 from two chunks up. */
 int hbls_aggrlc_final_selftest(int nchunks);
+/* where the combined path pairs the signatures: 0 = one
+ * Miller leg per item, 1 = one per chunk, on the sum of the chunk's scaled
+ * signatures, -1 = the default rule (1 from 16384 items).  Per-item results
+ * and hbls_aggrlc_last_stats are the same for both.  Other values return
+ * HBLS_ERR_BADINPUT and change nothing.  The environment variable
+ * HBLS_AGGRLC_SIGLEG (0/1) sets the initial one.  With leg 1,
+ * hbls_last_stage_ns(7) of the plain entries is the signature scaling and
+ * chunk sums, inside hbls_last_stage_ns(3). */
+int hbls_set_aggrlc_sigleg(int leg);
 
 /* batch Keccak-256 (consensus message digests, crypto/hash/hash.go:9-15) */
 int hbls_batch_keccak256(const uint8_t *msgs, size_t msg_len, size_t batch,

@@ -92,6 +92,26 @@ out["agg_verify_combined_stats"] = list(astats)
 assert list(astats) == [1, 0, 0]
 out["verify_stage_saving_per_item"] = (out["agg_verify_per_item_exact"] -
                                        out["agg_verify_per_item_combined"])
+# the combined path with the signature leg per item (leg 0) and once per chunk
+# (leg 1), same batch.  The front (mask, hash, decompress) is
+# the same launches in every mode, so the legs' difference is the verify
+# stage's; the verify-stage figures subtract the front as counted by the
+# single-item entries above.  The counter adds up what each lane's own control
+# flow performs: it does not see the additions a wave executes for the other
+# lanes' scalar bits in the bit-serial g1_mul / g2_mul.
+front = out["mask_aggregate_4096_b09"] + out["hash_to_g2"] + out["g2_check_sig"]
+out["front_per_item"] = front
+assert lib.hbls_set_agg_verify_mode(1) == 1
+for leg in (0, 1):
+    assert lib.hbls_set_aggrlc_sigleg(leg) == 1
+    out[f"agg_verify_per_item_combined_leg{leg}"] = count(
+        lambda: lib.hbls_batch_agg_verify(com, bm * nb, sig * nb, msg * nb, len(msg),
+                                          nb, bres)) // nb
+    assert list(bres) == [1] * nb, leg
+    out[f"verify_stage_per_item_combined_leg{leg}"] = (
+        out[f"agg_verify_per_item_combined_leg{leg}"] - front)
+out["verify_stage_per_item_exact"] = out["agg_verify_per_item_exact"] - front
+lib.hbls_set_aggrlc_sigleg(-1)
 lib.hbls_set_agg_verify_mode(-1)
 lib.hbls_set_aggrlc_threshold(-1)
 lib.hbls_set_coop_threshold(-1)
