@@ -120,6 +120,8 @@ def _load():
     lib.hbls_set_aggrlc_final.argtypes = [ctypes.c_int]
     lib.hbls_aggrlc_final_selftest.argtypes = [ctypes.c_int]
     lib.hbls_set_aggrlc_sigleg.argtypes = [ctypes.c_int]
+    lib.hbls_set_aggrlc_early.argtypes = [ctypes.c_int]
+    lib.hbls_set_aggrlc_chunkleg.argtypes = [ctypes.c_int]
     lib.hbls_aggrlc_probe.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
                                       ctypes.c_char_p]
     lib.hbls_last_host_ns.restype = ctypes.c_uint64
@@ -269,6 +271,24 @@ def set_aggrlc_sigleg(leg: int):
     Miller leg per item, 1 = one per chunk on the chunk's scaled signature
     sum, -1 = the default rule.  Verdicts and stats do not depend on it."""
     _check(_lib.hbls_set_aggrlc_sigleg(leg), "set_aggrlc_sigleg")
+
+
+def set_aggrlc_early(early: int):
+    """when the chunk-level signature leg is paired: 0 =
+    inside the Miller kernel, behind the items; 1 = hoisted: the signature
+    chain runs ahead of the mask kernel and the chunk legs beside it on a
+    side stream (plain, seal and quorum entries; ContextSet.seal_verify keeps
+    the sequence of 0); -1 = the default rule.  Verdicts and stats do not
+    depend on it.  last_stage_ns(8) is the chunk-leg kernel's own interval,
+    zero when nothing was hoisted."""
+    _check(_lib.hbls_set_aggrlc_early(early), "set_aggrlc_early")
+
+
+def set_aggrlc_chunkleg(kernel: int):
+    """kernel of the hoisted chunk legs: 16 = four lanes per
+    chunk, 16 chunks per block; 0 = one lane per chunk; -1 restores the
+    default.  Verdicts do not depend on it."""
+    _check(_lib.hbls_set_aggrlc_chunkleg(kernel), "set_aggrlc_chunkleg")
 
 
 AGGRLC_PROBE_OPS = {"g1_mul64w": (0, 3 * 48 + 8, 3 * 48),

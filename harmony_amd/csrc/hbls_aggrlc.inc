@@ -197,10 +197,21 @@ __global__ void k_aggrlc_miller(const g1_t *aggpubs, const g2_t *hms, const g2af
     results[i] = 1;      /* stands unless the chunk fails and is re-checked */
 }
 
+/* elig value of the hoisted schedule only (DESIGN.md §4l), between
+ * k_aggrlc_sigscale<true> and k_aggrlc_miller1<true>: an identity signature
+ * whose verdict waits for the key sum.  No later kernel sees it. */
+#define AGGRLC_ELIG_OPEN 3
+
 /* chunk-level signature leg, step 1 — thread per item: k_aggrlc_miller's
  * classification in its guard order (aggpubs[i] is read for g1_is_inf only),
  * then B_i = r_i*sig_i, Jacobian.  Classified items get elig 0 and B_i =
- * identity, so the chunk sum needs no flags. */
+ * identity, so the chunk sum needs no flags.
+ * HOISTED: the launch runs ahead of the mask kernel, so aggpubs does not
+ * exist yet and is not read.  The guard order stays, minus the key-sum test:
+ * an identity signature is left open (AGGRLC_ELIG_OPEN, B_i = identity), an
+ * item with a real signature is scaled whatever its key sum will be, and
+ * k_aggrlc_miller1<true> finishes both once it has the key sums. */
+template <bool HOISTED>
 __global__ void k_aggrlc_sigscale(const g1_t *aggpubs, const g2aff_t *sigs,
                                   const int32_t *sig_flags, const int32_t *hm_ok,
                                   const uint64_t *scalars, g2_t *B, int32_t *elig,
@@ -214,10 +225,14 @@ __global__ void k_aggrlc_sigscale(const g1_t *aggpubs, const g2aff_t *sigs,
         results[i] = HBLS_ERR_BADINPUT; B[i] = b; return;
     }
     bool sig_inf = sig_flags[i] == 2;
-    bool pub_inf = g1_is_inf(aggpubs[i]);
-    if (pub_inf || sig_inf) {
-        results[i] = (pub_inf && sig_inf) ? 1 : 0;   /* herumi edge */
-        B[i] = b; return;
+    if (HOISTED) {
+        if (sig_inf) { elig[i] = AGGRLC_ELIG_OPEN; B[i] = b; return; }
+    } else {
+        bool pub_inf = g1_is_inf(aggpubs[i]);
+        if (pub_inf || sig_inf) {
+            results[i] = (pub_inf && sig_inf) ? 1 : 0;   /* herumi edge */
+            B[i] = b; return;
+        }
     }
     uint64_t r = scalars[i];
     if (r == 0) r = 1;
@@ -233,14 +248,20 @@ __global__ void k_aggrlc_sigscale(const g1_t *aggpubs, const g2aff_t *sigs,
  * chunk's B_i, then lane 0 stores S_c affine.  sflag[c]: 1 = S[c] is an
  * affine point, 0 = the sum is the identity (no eligible item, or signatures
  * that cancel): its pairing value is one and the chunk entry contributes one;
- * the chunk's verdict still comes from the items' own factors. */
+ * the chunk's verdict still comes from the items' own factors.
+ * REPAIR (the hoisted schedule, after the Miller kernel): only the chunks
+ * marked dirty are summed again, over the items that are still eligible —
+ * the B_i of an item whose key sum turned out to be the identity drops out. */
+template <bool REPAIR>
 __global__ void __launch_bounds__(AGGRLC_CHUNK) k_aggrlc_sigsum(
-        const g2_t *B, int batch, int nchunks, g2aff_t *S, int32_t *sflag) {
+        const g2_t *B, int batch, int nchunks, g2aff_t *S, int32_t *sflag,
+        const int32_t *elig, const int32_t *dirty) {
     int c = blockIdx.x;
     if (c >= nchunks) return;
+    if (REPAIR && !dirty[c]) return;            /* uniform over the block */
     __shared__ g2_t red[AGGRLC_CHUNK];
     size_t i = (size_t)c * AGGRLC_CHUNK + threadIdx.x;
-    if (i < (size_t)batch) red[threadIdx.x] = B[i];
+    if (i < (size_t)batch && (!REPAIR || elig[i] != 0)) red[threadIdx.x] = B[i];
     else g2_set_inf(red[threadIdx.x]);
     __syncthreads();
     for (int s = AGGRLC_CHUNK / 2; s > 0; s >>= 1) {
@@ -268,11 +289,20 @@ __global__ void __launch_bounds__(AGGRLC_CHUNK) k_aggrlc_sigsum(
  * with elig 1: f(H_i; r_i*aggpk_i), or elig 2 when the scaled key sum is the
  * identity (as k_aggrlc_miller).  Thread batch + c: the chunk entry
  * f(S_c; -G1), one when sflag[c] is 0.  Both kinds meet in one call of the
- * loop, so the block that holds the boundary does not run it twice. */
+ * loop, so the block that holds the boundary does not run it twice.
+ * HOISTED (launched with nchunks = 0: the chunk entries have a kernel of
+ * their own, k_aggrlc_chunkleg): the item threads first finish what
+ * k_aggrlc_sigscale<true> could not decide without the key sums.  An open
+ * identity signature gets the herumi verdict.  An eligible item whose key
+ * sum is the identity is rejected as k_aggrlc_sigscale<false> would have
+ * done, and since its B_i is already inside S_c it marks the chunk dirty
+ * (every writer stores the same value) for the repair launches. */
+template <bool HOISTED>
 __global__ void k_aggrlc_miller1(const g1_t *aggpubs, const g2_t *hms,
                                  const uint64_t *scalars, const g2aff_t *S,
                                  const int32_t *sflag, fp12_t *F, int32_t *elig,
-                                 int32_t *results, int batch, int nchunks) {
+                                 int32_t *results, int batch, int nchunks,
+                                 int32_t *dirty) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)batch + (size_t)nchunks) return;
     fp12_t f;
@@ -280,6 +310,17 @@ __global__ void k_aggrlc_miller1(const g1_t *aggpubs, const g2_t *hms,
     g1aff_t P;
     bool run = false;
     if (i < (size_t)batch) {
+        if (HOISTED) {
+            int32_t e = elig[i];
+            if (e == AGGRLC_ELIG_OPEN) {
+                results[i] = g1_is_inf(aggpubs[i]) ? 1 : 0;      /* herumi edge */
+                elig[i] = 0;
+            } else if (e == 1 && g1_is_inf(aggpubs[i])) {
+                results[i] = 0;
+                elig[i] = 0;
+                dirty[i / AGGRLC_CHUNK] = 1;
+            }
+        }
         if (elig[i] == 1) {
             uint64_t r = scalars[i];
             if (r == 0) r = 1;
@@ -308,6 +349,108 @@ __global__ void k_aggrlc_miller1(const g1_t *aggpubs, const g2_t *hms,
     if (run) miller_loop1_h(f, Q, P);
     else fp12_one(f);
     F[i] = f;
+}
+
+/* the chunk entries of k_aggrlc_miller1 as a kernel of their own — thread
+ * per chunk: FX[c] = f(S_c; -G1), one when sflag[c] is 0.  The hoisted
+ * schedule runs it on a side stream beside the mask kernel, where its 64
+ * long waves take slots the short mask blocks leave, instead of behind a
+ * Miller grid that fills the chip exactly.  With `dirty` (the repair launch)
+ * only the chunks marked there are written again. */
+__global__ void k_aggrlc_chunkleg(const g2aff_t *S, const int32_t *sflag,
+                                  const int32_t *dirty, fp12_t *FX, int nchunks) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nchunks) return;
+    if (dirty && !dirty[c]) return;
+    fp12_t f;
+    if (sflag[c]) {
+        g2aff_t Q = S[c];
+        g1aff_t P;
+        fp_load(P.x, BLS_G1_X);
+        fp_t gy;
+        fp_load(gy, BLS_G1_Y);
+        fp_neg(P.y, gy);
+        miller_loop1_h(f, Q, P);
+    } else {
+        fp12_one(f);
+    }
+    FX[c] = f;
+}
+
+/* one leg of cv_miller2 (hbls_coop.inc): Q at CV_Q1 and P at CV_PP
+ * pre-loaded, result f at CV_F0 */
+DEVN void cv_miller1(lds_fp2 *A, int q) {
+    if (q == 0) {
+        lds_st(A + CV_T1, lds_ld(A + CV_Q1));
+        lds_st(A + (CV_T1 + 1), lds_ld(A + (CV_Q1 + 1)));
+        fp2_t one; fp_one(one.a); fp_zero(one.b);
+        lds_st(A + (CV_T1 + 2), one);
+    }
+    __syncthreads();
+    cv_fp12_set_one(A, q, CV_F0);
+    int cur = CV_F0, oth = CV_F1;
+    for (int bit = 62; bit >= 0; bit--) {
+        cv_fp12_sqr(A, q, oth, cur);
+        { int s = cur; cur = oth; oth = s; }
+        cv_ml_dbl_step(A, q, CV_T1, CV_PP);
+        cv_fp12_mul_line(A, q, oth, cur);
+        { int s = cur; cur = oth; oth = s; }
+        if ((BLS_U >> bit) & 1) {
+            cv_ml_add_step(A, q, CV_T1, CV_Q1, CV_PP);
+            cv_fp12_mul_line(A, q, oth, cur);
+            { int s = cur; cur = oth; oth = s; }
+        }
+    }
+    if (cur != CV_F0) cv_fp12_copy(A, q, CV_F0, cur);
+}
+
+/* the chunk entries on four lanes per chunk, ITEMS chunks per one-wave block
+ * in the arena layout of k_verify_coop: nchunks/ITEMS blocks spread over the
+ * chip and each leg's latency is a quarter-lane chain's, so the entries are
+ * done while the mask kernel still runs (DESIGN.md §4l).  The cooperative
+ * line functions scale their lines by subfield factors the one-lane steps do
+ * not, so FX[c] differs from k_aggrlc_chunkleg's by a factor the final
+ * exponentiation sends to one: the verdicts are the same.  Chunks with an
+ * identity sum, and the dummy sub-items of the last block, march through the
+ * loop on the G2 generator: control flow stays uniform across every barrier. */
+template <int ITEMS>
+__global__ void __launch_bounds__(ITEMS * CV_LANES) k_aggrlc_chunkleg_coop(
+        const g2aff_t *S, const int32_t *sflag, fp12_t *FX, int nchunks) {
+    __shared__ uint64_t arena[ITEMS][CV_STRIDE64];
+    __shared__ int32_t pre[ITEMS];   /* 1 computed; 0 one; -1 dummy */
+    const int sub = threadIdx.x / CV_LANES;
+    const int q = threadIdx.x % CV_LANES;
+    const int c = blockIdx.x * ITEMS + sub;
+    lds_fp2 *A = (lds_fp2 *)arena[sub];
+    if (q == 0) {
+        int32_t r = -1;
+        if (c < nchunks) r = sflag[c] ? 1 : 0;
+        pre[sub] = r;
+        g2aff_t Q;
+        if (r == 1) {
+            Q = S[c];
+        } else {
+            fp_load(Q.x.a, BLS_G2_XA); fp_load(Q.x.b, BLS_G2_XB);
+            fp_load(Q.y.a, BLS_G2_YA); fp_load(Q.y.b, BLS_G2_YB);
+        }
+        lds_st(A + (CV_Q1), Q.x); lds_st(A + (CV_Q1 + 1), Q.y);
+        fp2_t p;
+        fp_t gy;
+        fp_load(p.a, BLS_G1_X); fp_load(gy, BLS_G1_Y);
+        fp_neg(p.b, gy);                      /* -G1 */
+        lds_st(A + (CV_PP), p);
+    }
+    __syncthreads();
+    cv_miller1(A, q);
+    if (q == 0) {
+        int32_t r = pre[sub];
+        if (r != -1) {
+            fp12_t f;
+            if (r == 1) cv_ld_fp12(A, CV_F0, f);
+            else fp12_one(f);
+            FX[c] = f;
+        }
+    }
 }
 
 /* one block per chunk: LDS tree product of the chunk's eligible f values
@@ -496,6 +639,173 @@ extern "C" int hbls_set_aggrlc_sigleg(int leg) {
     return HBLS_OK;
 }
 
+/* when the chunk-level leg is paired (DESIGN.md §4l): 0 = inside the Miller
+ * kernel, behind the items; 1 = hoisted (AggrlcEarly below).  The default
+ * rule: hoisted from the smallest batch of the per-call sweep of §4l from
+ * which it does not lose the wall clock beyond the spread.  That is the
+ * largest one measured: below it the chunk entries ride in the Miller grid's
+ * partial last round for nothing, and hoisting only slows the mask kernel. */
+#define AGGRLC_EARLY_MIN_BATCH 262144
+static int g_aggrlc_early = -2;         /* -2: read env on first use; -1: the rule */
+static int aggrlc_early(size_t batch) {
+    if (g_aggrlc_early == -2) {
+        const char *e = getenv("HBLS_AGGRLC_EARLY");
+        int k = e ? atoi(e) : -1;
+        g_aggrlc_early = (k == 0 || k == 1) ? k : -1;
+    }
+    if (g_aggrlc_early >= 0) return g_aggrlc_early;
+    return batch >= AGGRLC_EARLY_MIN_BATCH ? 1 : 0;
+}
+extern "C" int hbls_set_aggrlc_early(int early) {
+    if (early < -1 || early > 1) return HBLS_ERR_BADINPUT;
+    g_aggrlc_early = early;
+    return HBLS_OK;
+}
+
+/* which kernel runs the hoisted chunk legs: 16 = four lanes per chunk, 16
+ * chunks per block (k_aggrlc_chunkleg_coop); 0 = one lane per chunk
+ * (k_aggrlc_chunkleg, which outlasts the mask kernel at the benchmark's size,
+ * DESIGN.md §4l, kept reproducible).  The repair launch is always the
+ * one-lane kernel: its clean chunks return at once. */
+#define AGGRLC_CHUNKLEG_DEFAULT 16
+static int g_aggrlc_chunkleg = -2;      /* -2: read env on first use */
+static int aggrlc_chunkleg_kernel(void) {
+    if (g_aggrlc_chunkleg == -2) {
+        const char *e = getenv("HBLS_AGGRLC_CHUNKLEG");
+        int k = e ? atoi(e) : AGGRLC_CHUNKLEG_DEFAULT;
+        g_aggrlc_chunkleg = (k == 0 || k == 16) ? k : AGGRLC_CHUNKLEG_DEFAULT;
+    }
+    return g_aggrlc_chunkleg;
+}
+extern "C" int hbls_set_aggrlc_chunkleg(int kernel) {
+    if (kernel == -1) kernel = AGGRLC_CHUNKLEG_DEFAULT;
+    if (kernel != 0 && kernel != 16) return HBLS_ERR_BADINPUT;
+    g_aggrlc_chunkleg = kernel;
+    return HBLS_OK;
+}
+
+/* the chunk legs' stream: non-blocking, created on first use and kept for
+ * the life of the process, like the upload stream */
+static hipStream_t g_aggrlc_side_stream = nullptr;
+static std::once_flag g_aggrlc_side_flag;
+static hipStream_t aggrlc_side_stream(void) {
+    std::call_once(g_aggrlc_side_flag, [] {
+        /* highest priority: where a chunk-leg block and a mask block compete
+         * for a slot, the few long blocks go first */
+        hipStream_t s = nullptr;
+        int least = 0, greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) {
+            (void)hipGetLastError();
+            greatest = 0;
+        }
+        if (hipStreamCreateWithPriority(&s, hipStreamNonBlocking, greatest) == hipSuccess)
+            g_aggrlc_side_stream = s;
+        else
+            (void)hipGetLastError();    /* no stream: nothing is hoisted */
+    });
+    return g_aggrlc_side_stream;
+}
+
+/* ---- the hoisted schedule (DESIGN.md §4l).  The chunk entries depend on
+ * the signature chain only (decompress, sigscale, sigsum), the item legs on
+ * hash and mask only.  run_agg_verify_pipeline therefore runs the signature
+ * chain ahead of the mask kernel and the chunk legs beside it:
+ *   hash, decompress, sigscale, sigsum, { mask | chunk legs on the side
+ *   stream }, Miller over the items, join, repair of dirty chunks, products,
+ *   final.
+ * This is everything the early part leaves behind for aggrlc_verify: device
+ * buffers that outlive their work (the destructor waits for the side stream
+ * before any of them is freed), the host scalars under the upload, and the
+ * events.  ev: 0..1 around sigscale + sigsum on the null stream (slot 7),
+ * 2..3 around the chunk-leg kernel on the side stream (slot 8), 4 the
+ * scalars' upload. */
+struct AggrlcEarly {
+    size_t batch, nc;
+    std::vector<uint64_t> scalars;
+    DevBuf dsc, dB, dS, dFX, delig, dflag;      /* dflag: sflag | dirty */
+    EventSet<5> ev;
+    bool launched = false;
+    AggrlcEarly(size_t b, size_t n)
+        : batch(b), nc(n), scalars(b), dsc(b * 8), dB(b * sizeof(g2_t)),
+          dS(n * sizeof(g2aff_t)), dFX(n * sizeof(fp12_t)), delig(b * 4), dflag(2 * n * 4) {}
+    bool ok() const {
+        return !dsc.err && !dB.err && !dS.err && !dFX.err && !delig.err && !dflag.err &&
+               ev.err == hipSuccess;
+    }
+    int32_t *sflag() const { return dflag.as<int32_t>(); }
+    int32_t *dirty() const { return dflag.as<int32_t>() + nc; }
+    ~AggrlcEarly() {
+        HostSpan sp(3);
+        if (launched) (void)hipStreamSynchronize(g_aggrlc_side_stream);
+    }
+};
+static void aggrlc_early_free(AggrlcEarly *e) { delete e; }
+
+/* the early part, called by the pipeline between the decompress and the
+ * mask launches.  Returns null — nothing launched, nothing written, the call
+ * proceeds as without it — unless the combined path with the chunk-level leg
+ * is taken, the switch allows it, and the scalars and every buffer are
+ * there.  When it returns the state, d_res and elig carry k_aggrlc_sigscale<true>'s
+ * classification, S and sflag the chunk sums, and the chunk legs are running
+ * on the side stream. */
+static AggrlcEarly *aggrlc_early_begin(const g2aff_t *d_saff, const int32_t *d_sflags,
+                                       const int32_t *d_hok, int32_t *d_res, size_t batch) {
+    if (!aggrlc_wanted(batch) || !aggrlc_sigleg(batch) || !aggrlc_early(batch)) return nullptr;
+    hipStream_t side = aggrlc_side_stream();
+    if (!side) return nullptr;
+    size_t nc = (batch + AGGRLC_CHUNK - 1) / AGGRLC_CHUNK;
+    uint64_t t_alloc = host_now_ns();
+    AggrlcEarly *st = new (std::nothrow) AggrlcEarly(batch, nc);
+    g_host_ns[0] += host_now_ns() - t_alloc;
+    if (!st) return nullptr;
+    if (!st->ok() || !rlc_draw_scalars(st->scalars.data(), batch)) {
+        (void)hipGetLastError();
+        delete st;
+        return nullptr;
+    }
+    bool good = upload_then_wait(st->dsc.p, st->scalars.data(), batch * 8, st->ev[4]) == hipSuccess;
+    st->launched = true;    /* from here on the destructor waits for the side stream */
+    good = good && hipMemsetAsync(st->dirty(), 0, nc * 4, 0) == hipSuccess;
+    if (!good) {
+        /* the null stream may hold the upload wait and the memset, which
+         * touch nothing the rest of the call reads */
+        (void)hipGetLastError();
+        (void)hipDeviceSynchronize();
+        delete st;
+        return nullptr;
+    }
+    (void)hipEventRecord(st->ev[0], 0);
+    hipLaunchKernelGGL(k_aggrlc_sigscale<true>, dim3((uint32_t)((batch + 63) / 64)), dim3(64), 0, 0,
+                       (const g1_t *)nullptr, d_saff, d_sflags, d_hok, st->dsc.as<uint64_t>(),
+                       st->dB.as<g2_t>(), st->delig.as<int32_t>(), d_res, (int)batch);
+    hipLaunchKernelGGL(k_aggrlc_sigsum<false>, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
+                       st->dB.as<g2_t>(), (int)batch, (int)nc, st->dS.as<g2aff_t>(), st->sflag(),
+                       (const int32_t *)nullptr, (const int32_t *)nullptr);
+    (void)hipEventRecord(st->ev[1], 0);
+    /* the side stream starts behind the chunk sums; its end event is waited
+     * for by aggrlc_verify, after the Miller launch */
+    (void)hipStreamWaitEvent(side, st->ev[1], 0);
+    (void)hipEventRecord(st->ev[2], side);
+    /* the null stream — the mask kernel is its next launch — waits for the
+     * side stream to have got as far as the chunk-leg launch: the legs' few
+     * blocks are then next in their own queue while the mask kernel still sits
+     * behind a cross-queue wait, and find the chip empty.  Launched at the
+     * same moment, the mask kernel's 65536 short blocks refill every slot as
+     * it frees and the legs' blocks, which need more registers and LDS than
+     * one retiring mask wave leaves, start late or outlast it (§4l). */
+    (void)hipStreamWaitEvent(0, st->ev[2], 0);
+    if (aggrlc_chunkleg_kernel() == 16)
+        hipLaunchKernelGGL(k_aggrlc_chunkleg_coop<16>, dim3((uint32_t)((nc + 15) / 16)),
+                           dim3(16 * CV_LANES), 0, side, st->dS.as<g2aff_t>(), st->sflag(),
+                           st->dFX.as<fp12_t>(), (int)nc);
+    else
+        hipLaunchKernelGGL(k_aggrlc_chunkleg, dim3((uint32_t)((nc + 63) / 64)), dim3(64), 0, side,
+                           st->dS.as<g2aff_t>(), st->sflag(), (const int32_t *)nullptr,
+                           st->dFX.as<fp12_t>(), (int)nc);
+    (void)hipEventRecord(st->ev[3], side);
+    return st;
+}
+
 static void launch_aggrlc_final(int kernel, const fp12_t *d_FC, const int32_t *d_ccnt,
                                 const int32_t *d_cforce, int32_t *d_verdict, int nc) {
     if (kernel == 16)
@@ -630,24 +940,32 @@ static bool aggrlc_wanted(size_t batch) {
  * device error.  g_stage_ns[4..6] = Miller, products, final exponentiation;
  * g_stage_ns[7] = the signature scaling and chunk sums of the chunk-level
  * leg (zero with the per-item leg).  Every launch lies between the caller's
- * verify-stage events. */
+ * verify-stage events.
+ * With `early` (the hoisted schedule) the scalars, the signature chain and
+ * the chunk legs are the pipeline's earlier work: what remains is the Miller
+ * kernel over the items, the join with the side stream, the repair of dirty
+ * chunks, products and final.  g_stage_ns[4] then covers the Miller kernel,
+ * the join and the repair launches, g_stage_ns[7] the early part's own
+ * interval and g_stage_ns[8] the chunk-leg kernel's on its stream. */
 static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_saff,
                          const int32_t *d_sflags, const int32_t *d_hok,
-                         int32_t *d_res, size_t batch) {
+                         int32_t *d_res, size_t batch, AggrlcEarly *early) {
     size_t nc = (batch + AGGRLC_CHUNK - 1) / AGGRLC_CHUNK;
-    const int leg = aggrlc_sigleg(batch);
-    const size_t nx = leg ? nc : 0;     /* chunk entries behind the items' f */
-    std::vector<uint64_t> scalars(batch);
-    if (!rlc_draw_scalars(scalars.data(), batch)) return AGGRLC_FALLBACK;
+    const int leg = early ? 1 : aggrlc_sigleg(batch);
+    const size_t nx = (leg && !early) ? nc : 0;     /* chunk entries behind the items' f */
+    std::vector<uint64_t> scalars(early ? 0 : batch);
+    if (!early && !rlc_draw_scalars(scalars.data(), batch)) return AGGRLC_FALLBACK;
     FreeClock fclk;
     uint64_t t_alloc = host_now_ns();
     /* dF: the items' f, then the chunk entries, then (chunk-level leg) the
      * scaled signatures B and the chunk sums S — one allocation, so the
      * per-item leg allocates what it always did; dcs: ccnt | cforce |
-     * verdict | sflag */
+     * verdict | sflag.  The hoisted schedule brings its own scalars, elig,
+     * B, S, sflag and chunk entries. */
     const size_t f_bytes = (batch + nx) * sizeof(fp12_t);
-    const size_t b_bytes = leg ? batch * sizeof(g2_t) : 0;
-    DevBuf dsc(batch * 8), dF(f_bytes + b_bytes + nx * sizeof(g2aff_t)), delig(batch * 4);
+    const size_t b_bytes = nx ? batch * sizeof(g2_t) : 0;
+    DevBuf dsc(early ? 0 : batch * 8), dF(f_bytes + b_bytes + nx * sizeof(g2aff_t));
+    DevBuf delig(early ? 0 : batch * 4);
     DevBuf dFC(nc * sizeof(fp12_t)), dcs((3 * nc + nx) * 4);
     g_host_ns[0] += host_now_ns() - t_alloc;
     FreeClockArm farm(fclk);
@@ -658,39 +976,57 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
     fp12_t *d_F = dF.as<fp12_t>();
     g2_t *d_B = (g2_t *)((uint8_t *)dF.p + f_bytes);
     g2aff_t *d_S = (g2aff_t *)((uint8_t *)dF.p + f_bytes + b_bytes);
+    const uint64_t *d_sc = early ? early->dsc.as<uint64_t>() : dsc.as<uint64_t>();
+    int32_t *d_elig = early ? early->delig.as<int32_t>() : delig.as<int32_t>();
     /* the scalars go up beside the kernels already queued, not behind them;
      * `scalars` outlives the copy (the verdict download below waits for the
      * Miller kernel, which waits for the upload) */
     EventSet<1> up;
     if (up.err != hipSuccess) return HBLS_ERR;
-    HIP_OK(upload_then_wait(dsc.p, scalars.data(), batch * 8, up[0]));
+    if (!early) HIP_OK(upload_then_wait(dsc.p, scalars.data(), batch * 8, up[0]));
     int32_t *d_ccnt = dcs.as<int32_t>(), *d_cforce = d_ccnt + nc, *d_verdict = d_cforce + nc;
     int32_t *d_sf = d_verdict + nc;
     /* ev[0..1] around the signature scaling and sums, ev[1..4] as before */
     EventSet<5> ev;
     if (ev.err != hipSuccess) return HBLS_ERR;
     (void)hipEventRecord(ev[0], 0);
-    if (leg) {
-        hipLaunchKernelGGL(k_aggrlc_sigscale, dim3((uint32_t)((batch + 63) / 64)), dim3(64), 0, 0,
-                           d_agg, d_saff, d_sflags, d_hok, dsc.as<uint64_t>(), d_B,
-                           delig.as<int32_t>(), d_res, (int)batch);
-        hipLaunchKernelGGL(k_aggrlc_sigsum, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
-                           d_B, (int)batch, (int)nc, d_S, d_sf);
+    if (leg && !early) {
+        hipLaunchKernelGGL(k_aggrlc_sigscale<false>, dim3((uint32_t)((batch + 63) / 64)), dim3(64),
+                           0, 0, d_agg, d_saff, d_sflags, d_hok, d_sc, d_B,
+                           d_elig, d_res, (int)batch);
+        hipLaunchKernelGGL(k_aggrlc_sigsum<false>, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
+                           d_B, (int)batch, (int)nc, d_S, d_sf,
+                           (const int32_t *)nullptr, (const int32_t *)nullptr);
     }
     (void)hipEventRecord(ev[1], 0);
-    if (leg)
-        hipLaunchKernelGGL(k_aggrlc_miller1, dim3((uint32_t)((batch + nc + 63) / 64)), dim3(64),
-                           0, 0, d_agg, d_hm, dsc.as<uint64_t>(), d_S, d_sf, d_F,
-                           delig.as<int32_t>(), d_res, (int)batch, (int)nc);
-    else
+    if (early) {
+        hipLaunchKernelGGL(k_aggrlc_miller1<true>, dim3((uint32_t)((batch + 63) / 64)), dim3(64),
+                           0, 0, d_agg, d_hm, d_sc, early->dS.as<g2aff_t>(), early->sflag(), d_F,
+                           d_elig, d_res, (int)batch, 0, early->dirty());
+        /* join: the chunk entries are complete; then the repair, over all
+         * chunks — blocks and threads of clean chunks return at once */
+        (void)hipStreamWaitEvent(0, early->ev[3], 0);
+        hipLaunchKernelGGL(k_aggrlc_sigsum<true>, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
+                           early->dB.as<g2_t>(), (int)batch, (int)nc, early->dS.as<g2aff_t>(),
+                           early->sflag(), d_elig, early->dirty());
+        hipLaunchKernelGGL(k_aggrlc_chunkleg, dim3((uint32_t)((nc + 63) / 64)), dim3(64), 0, 0,
+                           early->dS.as<g2aff_t>(), early->sflag(), early->dirty(),
+                           early->dFX.as<fp12_t>(), (int)nc);
+    } else if (leg) {
+        hipLaunchKernelGGL(k_aggrlc_miller1<false>, dim3((uint32_t)((batch + nc + 63) / 64)),
+                           dim3(64), 0, 0, d_agg, d_hm, d_sc, d_S, d_sf, d_F,
+                           d_elig, d_res, (int)batch, (int)nc, (int32_t *)nullptr);
+    } else {
         hipLaunchKernelGGL(k_aggrlc_miller, dim3((uint32_t)((batch + 63) / 64)), dim3(64), 0, 0,
-                           d_agg, d_hm, d_saff, d_sflags, d_hok, dsc.as<uint64_t>(),
-                           g_aggrlc_gtab, d_F, delig.as<int32_t>(), d_res, (int)batch);
+                           d_agg, d_hm, d_saff, d_sflags, d_hok, d_sc,
+                           g_aggrlc_gtab, d_F, d_elig, d_res, (int)batch);
+    }
     (void)hipEventRecord(ev[2], 0);
     hipLaunchKernelGGL(k_aggrlc_chunk_prod, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
-                       d_F, delig.as<int32_t>(), (int)batch, (int)nc,
+                       d_F, d_elig, (int)batch, (int)nc,
                        dFC.as<fp12_t>(), d_ccnt, d_cforce,
-                       leg ? d_F + batch : (const fp12_t *)nullptr);
+                       early ? early->dFX.as<fp12_t>()
+                             : leg ? d_F + batch : (const fp12_t *)nullptr);
     (void)hipEventRecord(ev[3], 0);
     launch_aggrlc_final(aggrlc_final_kernel(), dFC.as<fp12_t>(), d_ccnt, d_cforce,
                         d_verdict, (int)nc);
@@ -700,8 +1036,17 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
     if (e == hipSuccess) e = hipGetLastError();
     for (int i = 0; i < 4; i++) {
         float ms = 0;
-        if (e == hipSuccess && (i || leg)) (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
+        if (e == hipSuccess && (i || (leg && !early)))
+            (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
         g_stage_ns[i ? 3 + i : 7] = (uint64_t)(ms * 1e6);
+    }
+    if (early && e == hipSuccess) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, early->ev[0], early->ev[1]);
+        g_stage_ns[7] = (uint64_t)(ms * 1e6);
+        ms = 0;
+        (void)hipEventElapsedTime(&ms, early->ev[2], early->ev[3]);
+        g_stage_ns[8] = (uint64_t)(ms * 1e6);
     }
     HIP_OK(e);
 
@@ -718,7 +1063,7 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
     /* refinement, one level: the eligible items of failing chunks go through
      * the exact per-item pairing */
     std::vector<int32_t> helig(batch);
-    HIP_OK(hipMemcpy(helig.data(), delig.p, batch * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(helig.data(), d_elig, batch * 4, hipMemcpyDeviceToHost));
     std::vector<uint32_t> sel;
     for (uint32_t c : failed)
         for (size_t i = (size_t)c * AGGRLC_CHUNK;

@@ -454,6 +454,7 @@ extern "C" int hbls_batch_seal_verify_ctx(const hbls_ctxset_t *s, const uint32_t
     size_t nlive = idx.size();
     aggrlc_stats_reset();
     for (int i = 0; i < 7; i++) g_stage_ns[i] = 0;
+    g_stage_ns[8] = 0;          /* nothing is hoisted here (DESIGN.md §4l) */
     if (nlive == 0) {
         /* nothing to launch (a zero-block launch is an error) */
         for (size_t j = 0; j < batch; j++) results[j] = status[j];

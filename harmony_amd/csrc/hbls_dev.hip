@@ -2330,7 +2330,7 @@ static int coop_threshold(void) {
 }
 extern "C" void hbls_set_coop_threshold(int n) { g_coop_threshold = n; }
 static thread_local uint64_t g_last_ns = 0;
-static thread_local uint64_t g_stage_ns[8] = {0};
+static thread_local uint64_t g_stage_ns[9] = {0};
 static std::once_flag g_init_flag;
 static int g_init_rc = HBLS_ERR_NOGPU;
 /* combined aggregate verify (hbls_aggrlc.inc, included below) */
@@ -2373,7 +2373,7 @@ extern "C" int hbls_init(int device) {
 extern "C" void hbls_set_g2_cofactor_mode(int fast) { g_fast_cofactor = fast; }
 extern "C" const char *hbls_version(void) { return "hbls 0.1 (gfx950)"; }
 extern "C" uint64_t hbls_last_kernel_ns(void) { return g_last_ns; }
-extern "C" uint64_t hbls_last_stage_ns(int i) { return (i >= 0 && i < 8) ? g_stage_ns[i] : 0; }
+extern "C" uint64_t hbls_last_stage_ns(int i) { return (i >= 0 && i < 9) ? g_stage_ns[i] : 0; }
 
 static int require_gpu(void) {
     if (g_init_rc != HBLS_OK) {
@@ -2786,9 +2786,20 @@ extern "C" int hbls_mask_aggregate_g1(const hbls_committee_t *c, const uint8_t *
     return HBLS_OK;
 }
 
+/* the hoisted schedule of the combined path (hbls_aggrlc.inc, DESIGN.md
+ * §4l): the state its early part hands to aggrlc_verify, null when nothing
+ * was hoisted */
+struct AggrlcEarly;
+static AggrlcEarly *aggrlc_early_begin(const g2aff_t *d_saff, const int32_t *d_sflags,
+                                       const int32_t *d_hok, int32_t *d_res, size_t batch);
+static void aggrlc_early_free(AggrlcEarly *e);
+struct AggrlcEarlyHold {
+    AggrlcEarly *p = nullptr;
+    ~AggrlcEarlyHold() { if (p) aggrlc_early_free(p); }
+};
 static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_saff,
                          const int32_t *d_sflags, const int32_t *d_hok,
-                         int32_t *d_res, size_t batch);
+                         int32_t *d_res, size_t batch, AggrlcEarly *early);
 #define AGGRLC_FALLBACK 2       /* aggrlc_verify wrote nothing: run the exact path */
 
 /* host copies of the three inputs, for the entry point whose inputs are not
@@ -2801,16 +2812,20 @@ struct AggHostSrc { const uint8_t *bitmaps, *sigs, *msgs; };
  * stage intervals (ev[2s], ev[2s+1] around stage s; ev[2] is the call's
  * first event) and the verdicts to the host.  mode_batch is the batch size
  * the exact/combined rule is applied to.  Shared by run_agg_verify_pipeline
- * and the epoch-context entry (hbls_ctxset.inc). */
+ * and the epoch-context entry (hbls_ctxset.inc).  With `early` the pipeline
+ * has hoisted the combined path's signature chain, so the combined path it
+ * is; that chain's interval lies ahead of the verify events and is added to
+ * stage 3, so the four stages still add up to the call's kernel time. */
 static int run_agg_verify_pairing(const g1_t *d_agg, g2_t *d_hm, g2aff_t *d_saff,
                                   int32_t *d_sflags, int32_t *d_hok, int32_t *d_res,
                                   size_t batch, size_t mode_batch, const EventSet<8> &ev,
-                                  uint64_t t_launch, int32_t *results) {
+                                  uint64_t t_launch, int32_t *results,
+                                  AggrlcEarly *early = nullptr) {
     int nb = (int)((batch + 63) / 64);
     (void)hipEventRecord(ev[6], 0);
     int arc = AGGRLC_FALLBACK;
-    if (aggrlc_wanted(mode_batch)) {
-        arc = aggrlc_verify(d_agg, d_hm, d_saff, d_sflags, d_hok, d_res, batch);
+    if (early || aggrlc_wanted(mode_batch)) {
+        arc = aggrlc_verify(d_agg, d_hm, d_saff, d_sflags, d_hok, d_res, batch, early);
         if (arc != HBLS_OK && arc != AGGRLC_FALLBACK) return arc;
     }
     if (arc == HBLS_OK) {
@@ -2842,6 +2857,7 @@ static int run_agg_verify_pairing(const g1_t *d_agg, g2_t *d_hm, g2aff_t *d_saff
         (void)hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]);
         g_stage_ns[i] = (uint64_t)(ms * 1e6);
     }
+    if (early && arc == HBLS_OK) g_stage_ns[3] += g_stage_ns[7];
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(results, d_res, batch * 4, hipMemcpyDeviceToHost));
     g_host_ns[2] += host_now_ns() - t_launch;
@@ -2857,7 +2873,10 @@ static int run_agg_verify_pairing(const g1_t *d_agg, g2_t *d_hm, g2aff_t *d_saff
  * behind the hash and decompress kernels instead of in front of them.
  * g_stage_ns[0..3] stay mask, hash, decompress, verify: each the interval
  * between events recorded around that stage's launches (an upload wait sits
- * before the stage's first event). */
+ * before the stage's first event).  Where the combined path hoists its
+ * signature chain (aggrlc_early_begin) that chain runs between
+ * decompress and mask, outside the four intervals, and the chunk legs run
+ * beside the mask kernel on a side stream. */
 static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_bm,
                                    const uint8_t *d_sig, const uint8_t *d_msg,
                                    size_t msg_len, size_t batch, int32_t *results,
@@ -2874,7 +2893,7 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
         return HBLS_ERR;
     int nb = (int)((batch + 63) / 64);
     aggrlc_stats_reset();
-    for (int i = 4; i < 8; i++) g_stage_ns[i] = 0;    /* the combined path's own, if it runs */
+    for (int i = 4; i < 9; i++) g_stage_ns[i] = 0;    /* the combined path's own, if it runs */
     /* ev[2s], ev[2s+1] around stage s (0 mask, 1 hash, 2 decompress, 3 verify) */
     EventSet<8> ev;
     EventSet<3> up;
@@ -2905,6 +2924,13 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
     }
     (void)hipEventRecord(ev[5], 0);
 
+    /* the combined path's signature chain and chunk legs, ahead of and
+     * beside the mask kernel (declared after the buffers and events above:
+     * it waits for its side stream before they go) */
+    AggrlcEarlyHold early;
+    early.p = aggrlc_early_begin(dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), dhok.as<int32_t>(),
+                                 dres.as<int32_t>(), batch);
+
     if (src) HIP_OK(upload_then_wait((void *)d_bm, src->bitmaps, batch * bm, up[2]));
     (void)hipEventRecord(ev[0], 0);
     launch_mask_aggregate(c->d_table, (int)c->n, d_bm, (int)bm,
@@ -2914,7 +2940,7 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
 
     return run_agg_verify_pairing(dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
                                   dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(),
-                                  batch, batch, ev, t_launch, results);
+                                  batch, batch, ev, t_launch, results, early.p);
 }
 
 extern "C" int hbls_batch_agg_verify(const hbls_committee_t *c, const uint8_t *bitmaps,

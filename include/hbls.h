@@ -441,6 +441,25 @@ int hbls_aggrlc_final_selftest(int nchunks);
  * hbls_last_stage_ns(7) of the plain entries is the signature scaling and
  * chunk sums, inside hbls_last_stage_ns(3). */
 int hbls_set_aggrlc_sigleg(int leg);
+/* when leg 1's chunk entries are paired: 0 = inside the
+ * Miller kernel, behind the items; 1 = hoisted: signature scaling and chunk
+ * sums run ahead of the mask kernel and the chunk legs beside it on a side
+ * stream (hbls_batch_agg_verify, the seal and the quorum entries; the
+ * epoch-context entry keeps the sequence of 0); -1 = the default rule
+ * (hoisted from 262144 items).  Per-item results and
+ * hbls_aggrlc_last_stats are the same for both.  Other values return
+ * HBLS_ERR_BADINPUT and change nothing.  The environment variable
+ * HBLS_AGGRLC_EARLY (0/1) sets the initial one.  When hoisted,
+ * hbls_last_stage_ns(7) lies ahead of the mask stage and is counted into
+ * hbls_last_stage_ns(3); hbls_last_stage_ns(8) is the chunk-leg kernel's own
+ * interval on its stream (zero when nothing was hoisted) and
+ * hbls_last_stage_ns(4) includes the repair launches. */
+int hbls_set_aggrlc_early(int early);
+/* the kernel that runs the hoisted chunk legs: 16 = four lanes per chunk with
+ * 16 chunks per block, 0 = one lane per chunk, -1 restores the default (16).
+ * Verdicts are the same for both.  Other values return HBLS_ERR_BADINPUT.
+ * The environment variable HBLS_AGGRLC_CHUNKLEG (0/16) sets the initial one. */
+int hbls_set_aggrlc_chunkleg(int kernel);
 
 /* batch Keccak-256 (consensus message digests, crypto/hash/hash.go:9-15) */
 int hbls_batch_keccak256(const uint8_t *msgs, size_t msg_len, size_t batch,
