@@ -122,6 +122,7 @@ def _load():
     lib.hbls_set_aggrlc_sigleg.argtypes = [ctypes.c_int]
     lib.hbls_set_aggrlc_early.argtypes = [ctypes.c_int]
     lib.hbls_set_aggrlc_chunkleg.argtypes = [ctypes.c_int]
+    lib.hbls_set_aggrlc_miller.argtypes = [ctypes.c_int]
     lib.hbls_aggrlc_probe.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
                                       ctypes.c_char_p]
     lib.hbls_last_host_ns.restype = ctypes.c_uint64
@@ -291,15 +292,27 @@ def set_aggrlc_chunkleg(kernel: int):
     _check(_lib.hbls_set_aggrlc_chunkleg(kernel), "set_aggrlc_chunkleg")
 
 
+def set_aggrlc_miller(level: int):
+    """Miller kernel of the chunk-level leg's items: 0 =
+    affine arguments and a product kernel of its own; 1 = Jacobian arguments,
+    no inversion; 2 = that, and the chunk product inside the Miller kernel;
+    -1 restores the default.  Verdicts and stats do not depend on it."""
+    _check(_lib.hbls_set_aggrlc_miller(level), "set_aggrlc_miller")
+
+
 AGGRLC_PROBE_OPS = {"g1_mul64w": (0, 3 * 48 + 8, 3 * 48),
                     "g2_mul64w": (1, 6 * 48 + 8, 6 * 48),
-                    "miller1_fe": (2, 6 * 48, 12 * 48)}
+                    "miller1_fe": (2, 6 * 48, 12 * 48),
+                    "miller1j_fe": (3, 9 * 48, 12 * 48),
+                    "wave_prod": (4, 64 * 12 * 48, 2 * 12 * 48)}
 
 
 def aggrlc_probe(name: str, data: bytes, n_items: int) -> bytes:
-    """Test hook: run g1_mul64w / g2_mul64w (Jacobian point
-    and a little-endian u64 scalar per item) or miller1_fe (affine Q, affine
-    P) on raw device-domain limbs; returns the raw results."""
+    """Test hook: run g1_mul64w / g2_mul64w (Jacobian
+    point and a little-endian u64 scalar per item), miller1_fe (affine Q,
+    affine P), miller1j_fe (Jacobian Q, Jacobian P) or wave_prod (64 fp12 per
+    item; the product as held by lane 0 and by lane 63) on raw device-domain
+    limbs; returns the raw results."""
     op, in_b, out_b = AGGRLC_PROBE_OPS[name]
     if len(data) != n_items * in_b:
         raise ValueError("aggrlc_probe: operand size")

@@ -351,6 +351,158 @@ __global__ void k_aggrlc_miller1(const g1_t *aggpubs, const g2_t *hms,
     F[i] = f;
 }
 
+/* product of f over the 64 lanes of a wave, without LDS: six butterfly
+ * rounds (partner lane ^ 1, 2, 4, 8, 16, 32), each an exchange of the 72
+ * limbs and one multiplication in Fp12.  Every lane must be active.  Field
+ * results are canonical and the product commutes, so after round k the 2^k
+ * lanes of a group hold the same limbs and every lane ends with the wave's
+ * product.
+ * The first round is a whole fp12_mul per lane.  From the second round on
+ * the four lanes of an aligned quad hold the same unordered pair {x, y}, so
+ * the three Fp6 products of fp12_mul's Karatsuba step go one to a lane —
+ * lane 0 of the quad x0 y0, lane 1 x1 y1, lanes 2 and 3 (x0+x1)(y0+y1), each
+ * symmetric in x and y — and the quad reads them back: 18 fp-mul a round and
+ * lane in place of 54.
+ * Callers launch blocks of exactly 64 threads (blockDim.x == 64: the block is
+ * one wave and threadIdx.x the lane), and the result relies on every field
+ * operation returning the canonical representative below p, which the probe
+ * test pins limb for limb. */
+DEVN void fp12_wave_prod(fp12_t &f) {
+    union { fp12_t v; uint32_t w[144]; } a, b;
+    union { fp6_t v; uint32_t w[72]; } u, t0, t1, tt;
+    a.v = f;
+#pragma unroll
+    for (int i = 0; i < 144; i++) b.w[i] = (uint32_t)__shfl_xor((int)a.w[i], 1, 64);
+    fp12_mul(a.v, a.v, b.v);
+    const int lane = (int)(threadIdx.x & 63u), role = lane & 3, quad = lane & ~3;
+    for (int m = 2; m < 64; m <<= 1) {
+#pragma unroll
+        for (int i = 0; i < 144; i++) b.w[i] = (uint32_t)__shfl_xor((int)a.w[i], m, 64);
+        fp6_t p, q;
+        fp6_add(p, a.v.c0, a.v.c1);
+        fp6_add(q, b.v.c0, b.v.c1);
+        if (role == 0) { p = a.v.c0; q = b.v.c0; }
+        if (role == 1) { p = a.v.c1; q = b.v.c1; }
+        fp6_mul(u.v, p, q);
+#pragma unroll
+        for (int i = 0; i < 72; i++) {
+            t0.w[i] = (uint32_t)__shfl((int)u.w[i], quad, 64);
+            t1.w[i] = (uint32_t)__shfl((int)u.w[i], quad + 1, 64);
+            tt.w[i] = (uint32_t)__shfl((int)u.w[i], quad + 2, 64);
+        }
+        fp6_sub(tt.v, tt.v, t0.v);
+        fp6_sub(a.v.c1, tt.v, t1.v);
+        fp6_mul_v(u.v, t1.v);
+        fp6_add(a.v.c0, t0.v, u.v);
+    }
+    f = a.v;
+}
+
+/* k_aggrlc_miller1 without the two inversions at its head (DESIGN.md §4m):
+ * an item thread hands r_i*aggpk_i and H_i to miller_loop1_hj as they are,
+ * Jacobian.  A hash point with Z = 0 — which hashing cannot produce — is
+ * treated like an identity key sum: elig 2, so that no input skips its
+ * pairing.  The chunk entries (affine S_c, -G1) keep miller_loop1_h, so
+ * unlike k_aggrlc_miller1 the two kinds do not meet in one call of a loop:
+ * the not-hoisted instantiations carry both loops, and in <false, false> the
+ * one wave that holds the last items and the first entries (batch not a
+ * multiple of 64) runs them one after the other — one wave, at the kernel's
+ * tail.  <false, true> has no such wave: its entries have blocks of their own.
+ * FUSED: the block is the chunk.  Blocks 0..nchunks-1 hold the items, lane l
+ * of block c is item 64c + l, and no thread leaves before the product: lanes
+ * past the batch, classified items and items this kernel demotes hold one.
+ * The product is taken across the wave (fp12_wave_prod) and lane 0 stores
+ * FC[c], ccnt[c] and cforce[c] with k_aggrlc_chunk_prod's meaning; F does not
+ * exist.  Blocks from nchunks on, present in the launch when the chunk
+ * entries are not hoisted, are the chunk entries: thread per chunk, FX[c]. */
+template <bool HOISTED, bool FUSED>
+__global__ void k_aggrlc_miller1j(const g1_t *aggpubs, const g2_t *hms,
+                                  const uint64_t *scalars, const g2aff_t *S,
+                                  const int32_t *sflag, fp12_t *F, int32_t *elig,
+                                  int32_t *results, int batch, int nchunks,
+                                  int32_t *dirty, fp12_t *FC, int32_t *ccnt,
+                                  int32_t *cforce) {
+    const bool item_block = !FUSED || (int)blockIdx.x < nchunks;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    size_t c = 0;
+    bool is_item, is_entry;
+    if (FUSED) {
+        is_item = item_block && i < (size_t)batch;
+        c = i - (size_t)nchunks * blockDim.x;
+        is_entry = !HOISTED && !item_block && c < (size_t)nchunks;
+        if (!item_block && !is_entry) return;
+    } else {
+        if (i >= (size_t)batch + (size_t)nchunks) return;
+        is_item = i < (size_t)batch;
+        is_entry = !is_item;
+        c = i - (size_t)batch;
+    }
+    fp12_t f;
+    int32_t e = 0;
+    bool run = false;
+    if (is_item) {
+        e = elig[i];
+        if (HOISTED) {
+            if (e == AGGRLC_ELIG_OPEN) {
+                results[i] = g1_is_inf(aggpubs[i]) ? 1 : 0;      /* herumi edge */
+                elig[i] = e = 0;
+            } else if (e == 1 && g1_is_inf(aggpubs[i])) {
+                results[i] = 0;
+                elig[i] = e = 0;
+                dirty[i / AGGRLC_CHUNK] = 1;
+            }
+        }
+        if (e == 1) {
+            uint64_t r = scalars[i];
+            if (r == 0) r = 1;
+            g1_t A;
+            g1_mul64w(A, aggpubs[i], r);
+            g2_t hmc = hms[i];
+            if (g1_is_inf(A) || g2_is_inf(hmc)) {
+                elig[i] = e = 2; results[i] = 0;
+            } else {
+                miller_loop1_hj(f, hmc, A);
+                run = true;
+            }
+        }
+    } else if (!HOISTED && is_entry) {
+        if (sflag[c]) {
+            g2aff_t Q = S[c];
+            g1aff_t P;
+            fp_load(P.x, BLS_G1_X);
+            fp_t gy;
+            fp_load(gy, BLS_G1_Y);
+            fp_neg(P.y, gy);
+            miller_loop1_h(f, Q, P);
+            run = true;
+        }
+    }
+    if (!run) fp12_one(f);
+    if (!FUSED) {
+        F[i] = f;
+    } else if (!item_block) {
+        F[c] = f;                       /* the chunk entries' buffer, FX */
+    } else {
+        fp12_wave_prod(f);
+        unsigned long long any = __ballot(e != 0), force = __ballot(e == 2);
+        if (threadIdx.x == 0) {
+            FC[blockIdx.x] = f;
+            ccnt[blockIdx.x] = __popcll(any);
+            cforce[blockIdx.x] = force ? 1 : 0;
+        }
+    }
+}
+
+/* thread per chunk: the chunk's own entry into the product the fused Miller
+ * kernel left in FC — what lane 0 of k_aggrlc_chunk_prod does after its tree */
+__global__ void k_aggrlc_chunk_fold(fp12_t *FC, const fp12_t *FX, int nchunks) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nchunks) return;
+    fp12_t a = FC[c], b = FX[c];
+    fp12_mul(a, a, b);
+    FC[c] = a;
+}
+
 /* the chunk entries of k_aggrlc_miller1 as a kernel of their own — thread
  * per chunk: FX[c] = f(S_c; -G1), one when sflag[c] is 0.  The hoisted
  * schedule runs it on a side stream beside the mask kernel, where its 64
@@ -662,6 +814,28 @@ extern "C" int hbls_set_aggrlc_early(int early) {
     return HBLS_OK;
 }
 
+/* which Miller kernel runs leg 1's items (DESIGN.md §4m): 0 = k_aggrlc_miller1
+ * (affine arguments, F to memory, k_aggrlc_chunk_prod); 1 = Jacobian
+ * arguments, no inversion (k_aggrlc_miller1j); 2 = that, and the chunk
+ * product inside the kernel (no F, k_aggrlc_chunk_fold).  The default is the
+ * highest level that won the per-call sweep of §4m by the project's rule. */
+#define AGGRLC_MILLER_DEFAULT 2
+static int g_aggrlc_miller = -2;        /* -2: read env on first use */
+static int aggrlc_miller_level(void) {
+    if (g_aggrlc_miller == -2) {
+        const char *e = getenv("HBLS_AGGRLC_MILLER");
+        /* exactly "0", "1" or "2": anything else, a typo included, is the default */
+        bool digit = e && e[0] >= '0' && e[0] <= '2' && e[1] == '\0';
+        g_aggrlc_miller = digit ? e[0] - '0' : AGGRLC_MILLER_DEFAULT;
+    }
+    return g_aggrlc_miller;
+}
+extern "C" int hbls_set_aggrlc_miller(int level) {
+    if (level < -1 || level > 2) return HBLS_ERR_BADINPUT;
+    g_aggrlc_miller = level == -1 ? AGGRLC_MILLER_DEFAULT : level;
+    return HBLS_OK;
+}
+
 /* which kernel runs the hoisted chunk legs: 16 = four lanes per chunk, 16
  * chunks per block (k_aggrlc_chunkleg_coop); 0 = one lane per chunk
  * (k_aggrlc_chunkleg, which outlasts the mask kernel at the benchmark's size,
@@ -953,6 +1127,8 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
     size_t nc = (batch + AGGRLC_CHUNK - 1) / AGGRLC_CHUNK;
     const int leg = early ? 1 : aggrlc_sigleg(batch);
     const size_t nx = (leg && !early) ? nc : 0;     /* chunk entries behind the items' f */
+    const int lvl = leg ? aggrlc_miller_level() : 0;
+    const bool fused = lvl == 2;                    /* no F: the Miller kernel stores FC */
     std::vector<uint64_t> scalars(early ? 0 : batch);
     if (!early && !rlc_draw_scalars(scalars.data(), batch)) return AGGRLC_FALLBACK;
     FreeClock fclk;
@@ -962,7 +1138,8 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
      * per-item leg allocates what it always did; dcs: ccnt | cforce |
      * verdict | sflag.  The hoisted schedule brings its own scalars, elig,
      * B, S, sflag and chunk entries. */
-    const size_t f_bytes = (batch + nx) * sizeof(fp12_t);
+    const size_t nf = fused ? 0 : batch;
+    const size_t f_bytes = (nf + nx) * sizeof(fp12_t);
     const size_t b_bytes = nx ? batch * sizeof(g2_t) : 0;
     DevBuf dsc(early ? 0 : batch * 8), dF(f_bytes + b_bytes + nx * sizeof(g2aff_t));
     DevBuf delig(early ? 0 : batch * 4);
@@ -1000,9 +1177,21 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
     }
     (void)hipEventRecord(ev[1], 0);
     if (early) {
-        hipLaunchKernelGGL(k_aggrlc_miller1<true>, dim3((uint32_t)((batch + 63) / 64)), dim3(64),
-                           0, 0, d_agg, d_hm, d_sc, early->dS.as<g2aff_t>(), early->sflag(), d_F,
-                           d_elig, d_res, (int)batch, 0, early->dirty());
+        if (fused)
+            hipLaunchKernelGGL((k_aggrlc_miller1j<true, true>), dim3((uint32_t)nc), dim3(64),
+                               0, 0, d_agg, d_hm, d_sc, early->dS.as<g2aff_t>(), early->sflag(),
+                               d_F, d_elig, d_res, (int)batch, (int)nc, early->dirty(),
+                               dFC.as<fp12_t>(), d_ccnt, d_cforce);
+        else if (lvl == 1)
+            hipLaunchKernelGGL((k_aggrlc_miller1j<true, false>),
+                               dim3((uint32_t)((batch + 63) / 64)), dim3(64),
+                               0, 0, d_agg, d_hm, d_sc, early->dS.as<g2aff_t>(), early->sflag(),
+                               d_F, d_elig, d_res, (int)batch, 0, early->dirty(),
+                               (fp12_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
+        else
+            hipLaunchKernelGGL(k_aggrlc_miller1<true>, dim3((uint32_t)((batch + 63) / 64)),
+                               dim3(64), 0, 0, d_agg, d_hm, d_sc, early->dS.as<g2aff_t>(),
+                               early->sflag(), d_F, d_elig, d_res, (int)batch, 0, early->dirty());
         /* join: the chunk entries are complete; then the repair, over all
          * chunks — blocks and threads of clean chunks return at once */
         (void)hipStreamWaitEvent(0, early->ev[3], 0);
@@ -1012,6 +1201,18 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
         hipLaunchKernelGGL(k_aggrlc_chunkleg, dim3((uint32_t)((nc + 63) / 64)), dim3(64), 0, 0,
                            early->dS.as<g2aff_t>(), early->sflag(), early->dirty(),
                            early->dFX.as<fp12_t>(), (int)nc);
+    } else if (fused) {
+        /* nc item blocks, then the chunk entries, thread per chunk, into d_F */
+        hipLaunchKernelGGL((k_aggrlc_miller1j<false, true>),
+                           dim3((uint32_t)(nc + (nc + 63) / 64)), dim3(64), 0, 0, d_agg, d_hm,
+                           d_sc, d_S, d_sf, d_F, d_elig, d_res, (int)batch, (int)nc,
+                           (int32_t *)nullptr, dFC.as<fp12_t>(), d_ccnt, d_cforce);
+    } else if (lvl == 1) {
+        hipLaunchKernelGGL((k_aggrlc_miller1j<false, false>),
+                           dim3((uint32_t)((batch + nc + 63) / 64)), dim3(64), 0, 0, d_agg, d_hm,
+                           d_sc, d_S, d_sf, d_F, d_elig, d_res, (int)batch, (int)nc,
+                           (int32_t *)nullptr, (fp12_t *)nullptr, (int32_t *)nullptr,
+                           (int32_t *)nullptr);
     } else if (leg) {
         hipLaunchKernelGGL(k_aggrlc_miller1<false>, dim3((uint32_t)((batch + nc + 63) / 64)),
                            dim3(64), 0, 0, d_agg, d_hm, d_sc, d_S, d_sf, d_F,
@@ -1022,11 +1223,15 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
                            g_aggrlc_gtab, d_F, d_elig, d_res, (int)batch);
     }
     (void)hipEventRecord(ev[2], 0);
-    hipLaunchKernelGGL(k_aggrlc_chunk_prod, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
-                       d_F, d_elig, (int)batch, (int)nc,
-                       dFC.as<fp12_t>(), d_ccnt, d_cforce,
-                       early ? early->dFX.as<fp12_t>()
-                             : leg ? d_F + batch : (const fp12_t *)nullptr);
+    const fp12_t *d_FX = early ? early->dFX.as<fp12_t>()
+                               : leg ? d_F + nf : (const fp12_t *)nullptr;
+    if (fused)
+        hipLaunchKernelGGL(k_aggrlc_chunk_fold, dim3((uint32_t)((nc + 63) / 64)), dim3(64), 0, 0,
+                           dFC.as<fp12_t>(), d_FX, (int)nc);
+    else
+        hipLaunchKernelGGL(k_aggrlc_chunk_prod, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
+                           d_F, d_elig, (int)batch, (int)nc,
+                           dFC.as<fp12_t>(), d_ccnt, d_cforce, d_FX);
     (void)hipEventRecord(ev[3], 0);
     launch_aggrlc_final(aggrlc_final_kernel(), dFC.as<fp12_t>(), d_ccnt, d_cforce,
                         d_verdict, (int)nc);
@@ -1090,9 +1295,14 @@ static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_s
  *   1 g2_mul64w   in Jacobian point (6 fp) | u64 scalar   out Jacobian (6 fp)
  *   2 miller1_fe  in affine Q (4 fp) | affine P (2 fp)    out fp12 (12 fp):
  *                 final_exp(conj(miller_loop1_h(Q, P))), what the final
- *                 kernels apply to a chunk product */
+ *                 kernels apply to a chunk product
+ *   3 miller1j_fe in Jacobian Q (6 fp) | Jacobian P (3 fp) out fp12 (12 fp):
+ *                 final_exp(conj(miller_loop1_hj(Q, P)))
+ *   4 wave_prod   in 64 fp12 (768 fp), one 64-lane block per item
+ *                 out fp12_wave_prod as held by lane 0 | by lane 63 (24 fp) */
 enum { AGGRLC_PROBE_G1_MUL64W = 0, AGGRLC_PROBE_G2_MUL64W = 1, AGGRLC_PROBE_MILLER1_FE = 2,
-       AGGRLC_PROBE_N_OPS = 3 };
+       AGGRLC_PROBE_MILLER1J_FE = 3, AGGRLC_PROBE_WAVE_PROD = 4, AGGRLC_PROBE_N_OPS = 5 };
+#define AGGRLC_PROBE_MAX_GROUPS 64
 #define AGGRLC_PROBE_MAX_ITEMS 4096
 __global__ void k_aggrlc_probe(int op, const uint64_t *in, int in_w, uint64_t *out, int out_w,
                                int n) {
@@ -1106,6 +1316,15 @@ __global__ void k_aggrlc_probe(int op, const uint64_t *in, int in_w, uint64_t *o
         g1_mul64w(o.g1, a.g1, src[18]);
     } else if (op == AGGRLC_PROBE_G2_MUL64W) {
         g2_mul64w(o.g2, a.g2, src[36]);
+    } else if (op == AGGRLC_PROBE_MILLER1J_FE) {
+        g1_t p;
+        for (int k = 0; k < 6; k++) {
+            p.x.l[k] = src[36 + k]; p.y.l[k] = src[42 + k]; p.z.l[k] = src[48 + k];
+        }
+        fp12_t f;
+        miller_loop1_hj(f, a.g2, p);
+        fp12_conj(f, f);
+        final_exp(o.f, f);
     } else {
         g1aff_t p;
         for (int k = 0; k < 6; k++) { p.x.l[k] = src[24 + k]; p.y.l[k] = src[30 + k]; }
@@ -1116,14 +1335,28 @@ __global__ void k_aggrlc_probe(int op, const uint64_t *in, int in_w, uint64_t *o
     }
     for (int i = 0; i < out_w; i++) dst[i] = o.w[i];
 }
+/* block per group of 64 elements, lane l holds element l */
+__global__ void k_aggrlc_probe_wave_prod(const fp12_t *in, fp12_t *out, int n) {
+    int g = blockIdx.x;
+    if (g >= n) return;
+    fp12_t f = in[(size_t)g * 64 + threadIdx.x];
+    fp12_wave_prod(f);
+    if (threadIdx.x == 0) out[2 * g] = f;
+    if (threadIdx.x == 63) out[2 * g + 1] = f;
+}
 static bool probe_limbs_lt_p(const uint8_t *b);     /* hbls_probe.inc */
 extern "C" int hbls_aggrlc_probe(int op, const uint8_t *in, size_t n_items, uint8_t *out) {
     if (op < 0 || op >= AGGRLC_PROBE_N_OPS) return HBLS_ERR_BADINPUT;
     if (!in || !out || n_items == 0 || n_items > AGGRLC_PROBE_MAX_ITEMS)
         return HBLS_ERR_BADINPUT;
-    const int n_fp = op == AGGRLC_PROBE_G1_MUL64W ? 3 : 6;       /* fp elements in */
-    const int in_w = n_fp * 6 + (op == AGGRLC_PROBE_MILLER1_FE ? 0 : 1);
-    const int out_w = op == AGGRLC_PROBE_G1_MUL64W ? 18 : op == AGGRLC_PROBE_G2_MUL64W ? 36 : 72;
+    const bool wave = op == AGGRLC_PROBE_WAVE_PROD;
+    if (wave && n_items > AGGRLC_PROBE_MAX_GROUPS) return HBLS_ERR_BADINPUT;
+    const bool mul = op == AGGRLC_PROBE_G1_MUL64W || op == AGGRLC_PROBE_G2_MUL64W;
+    const int n_fp = op == AGGRLC_PROBE_G1_MUL64W ? 3 : op == AGGRLC_PROBE_MILLER1J_FE ? 9
+                     : wave ? 64 * 12 : 6;                      /* fp elements in */
+    const int in_w = n_fp * 6 + (mul ? 1 : 0);
+    const int out_w = op == AGGRLC_PROBE_G1_MUL64W ? 18 : op == AGGRLC_PROBE_G2_MUL64W ? 36
+                      : wave ? 144 : 72;
     for (size_t j = 0; j < n_items; j++)
         for (int i = 0; i < n_fp; i++)
             if (!probe_limbs_lt_p(in + j * (size_t)in_w * 8 + 48 * i)) return HBLS_ERR_BADINPUT;
@@ -1132,8 +1365,12 @@ extern "C" int hbls_aggrlc_probe(int op, const uint8_t *in, size_t n_items, uint
     DevBuf din(n_items * in_w * 8), dout(n_items * out_w * 8);
     if (din.err || dout.err) return HBLS_ERR;
     HIP_OK(hipMemcpy(din.p, in, n_items * in_w * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_aggrlc_probe, dim3((uint32_t)((n_items + 63) / 64)), dim3(64), 0, 0,
-                       op, din.as<uint64_t>(), in_w, dout.as<uint64_t>(), out_w, (int)n_items);
+    if (wave)
+        hipLaunchKernelGGL(k_aggrlc_probe_wave_prod, dim3((uint32_t)n_items), dim3(64), 0, 0,
+                           din.as<fp12_t>(), dout.as<fp12_t>(), (int)n_items);
+    else
+        hipLaunchKernelGGL(k_aggrlc_probe, dim3((uint32_t)((n_items + 63) / 64)), dim3(64), 0, 0,
+                           op, din.as<uint64_t>(), in_w, dout.as<uint64_t>(), out_w, (int)n_items);
     HIP_OK(hipGetLastError());
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(out, dout.p, n_items * out_w * 8, hipMemcpyDeviceToHost));

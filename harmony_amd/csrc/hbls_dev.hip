@@ -1284,6 +1284,80 @@ DEVN void ml_add_step_h(g2_t &T, const g2aff_t &Q, const g1aff_t &Pa,
     fp2_sub(T.y, t, t2);
     fp2_mul(T.z, T.z, E);
 }
+/* ---- the same steps on arguments that were never made affine (DESIGN.md
+ * §4m; executable spec in tests/test_miller_jac_formulas.py).
+ * Full addition T += Q2 with Q2 = (X2, Y2, Z2) homogeneous:
+ *   theta' = Y Z2 - Y2 Z = Z2 theta,  lambda' = X Z2 - X2 Z = Z2 lambda,
+ * the line of ml_add_step_h scaled by Z2^2 and the point by Z2^4 (the same
+ * projective point).  Pp = (xP k, yP k) for a k in Fp, and c3 is multiplied
+ * by the same k: the whole line is k times ml_add_step_h's. */
+DEVN void ml_add_step_hj(g2_t &T, const g2_t &Q2, const g1aff_t &Pp, const fp_t &k,
+                         fp2_t &c0, fp2_t &c3, fp2_t &c5) {
+    fp2_t th, la, yz, xz, zz, C, D, E, F, G, H, t, t2;
+    fp2_mul(yz, T.y, Q2.z);
+    fp2_mul(t, Q2.y, T.z);
+    fp2_sub(th, yz, t);
+    fp2_mul(xz, T.x, Q2.z);
+    fp2_mul(t, Q2.x, T.z);
+    fp2_sub(la, xz, t);
+    fp2_mul(zz, T.z, Q2.z);
+    fp2_mul(t, la, Q2.z);
+    fp2_mul_fp(t, t, Pp.y);
+    fp2_mul_xi(c0, t);                   /* xi yP lambda' Z2 */
+    fp2_mul(t, Q2.x, th);
+    fp2_mul(t2, Q2.y, la);
+    fp2_sub(t, t, t2);
+    fp2_mul_fp(c3, t, k);                /* X2 theta' - Y2 lambda' */
+    fp2_mul(t, th, Q2.z);
+    fp2_mul_fp(t, t, Pp.x);
+    fp2_neg(c5, t);                      /* -theta' Z2 xP */
+    fp2_sqr(C, th);
+    fp2_sqr(D, la);
+    fp2_mul(E, la, D);
+    fp2_mul(F, zz, C);
+    fp2_mul(G, xz, D);
+    fp2_add(H, E, F);
+    fp2_dbl(t, G);
+    fp2_sub(H, H, t);
+    fp2_mul(T.x, la, H);
+    fp2_sub(t, G, H);
+    fp2_mul(t, th, t);
+    fp2_mul(t2, E, yz);
+    fp2_sub(T.y, t, t2);
+    fp2_mul(T.z, zz, E);
+}
+/* f = f_{|z|,Q}(P) up to subfield factors for Jacobian Q = (X, Y, Z) and
+ * P = (x, y, z), both with a nonzero third coordinate: no inversion.
+ * G1: xP = x/z^2, yP = y/z^3; every line is multiplied by k = z^3 in Fp, so
+ * the steps get (x z, y) where they use (xP, yP) and c3 is multiplied by k.
+ * G2: T starts at the homogeneous form (X Z, Y, Z^3) of Q, which the
+ * additions use as it is. */
+DEVN void miller_loop1_hj(fp12_t &f, const g2_t &Qj, const g1_t &Pj) {
+    g1aff_t Pp;
+    fp_t k;
+    fp_sqr(k, Pj.z);
+    fp_mul(k, k, Pj.z);
+    fp_mul(Pp.x, Pj.x, Pj.z);
+    Pp.y = Pj.y;
+    g2_t Q2, T;
+    fp2_t c0, c3, c5;
+    fp2_sqr(c0, Qj.z);
+    fp2_mul(Q2.z, c0, Qj.z);
+    fp2_mul(Q2.x, Qj.x, Qj.z);
+    Q2.y = Qj.y;
+    T = Q2;
+    fp12_one(f);
+    for (int bit = 62; bit >= 0; bit--) {
+        fp12_sqr(f, f);
+        ml_dbl_step_h(T, Pp, c0, c3, c5);
+        fp2_mul_fp(c3, c3, k);
+        fp12_mul_line(f, c0, c3, c5);
+        if ((BLS_U >> bit) & 1) {
+            ml_add_step_hj(T, Q2, Pp, k, c0, c3, c5);
+            fp12_mul_line(f, c0, c3, c5);
+        }
+    }
+}
 /* f *= l1 * l2 for two lines a0 + (a3 v + a5 v^2) w, b0 + (b3 v + b5 v^2) w.
  * Their product m = m0 + m1 w has m0 full and m1 = (0, x, y): 6 fp2-mul.
  * Folding m into f takes f0*m0 (6), f1*m1 (5, Karatsuba on the 2-sparse

@@ -460,6 +460,18 @@ int hbls_set_aggrlc_early(int early);
  * Verdicts are the same for both.  Other values return HBLS_ERR_BADINPUT.
  * The environment variable HBLS_AGGRLC_CHUNKLEG (0/16) sets the initial one. */
 int hbls_set_aggrlc_chunkleg(int kernel);
+/* the Miller kernel of leg 1's items: 0 = affine arguments
+ * (two inversions per item), per-item values stored and multiplied by a
+ * kernel of their own; 1 = Jacobian arguments, no inversion; 2 = that, and
+ * the chunk product taken inside the Miller kernel, across the lanes of the
+ * wave that is the chunk; -1 restores the default (2).  Honoured wherever
+ * leg 1 runs, hoisted or not, the epoch-context entry included.  Per-item
+ * results and hbls_aggrlc_last_stats are the same for every level.  Other
+ * values return HBLS_ERR_BADINPUT and change nothing.  The environment
+ * variable HBLS_AGGRLC_MILLER (0/1/2) sets the initial one.
+ * hbls_last_stage_ns(5) is the chunk products' interval at every level: at 2
+ * only the chunk entries' one multiplication per chunk is left in it. */
+int hbls_set_aggrlc_miller(int level);
 
 /* batch Keccak-256 (consensus message digests, crypto/hash/hash.go:9-15) */
 int hbls_batch_keccak256(const uint8_t *msgs, size_t msg_len, size_t batch,

@@ -111,6 +111,20 @@ for leg in (0, 1):
     out[f"verify_stage_per_item_combined_leg{leg}"] = (
         out[f"agg_verify_per_item_combined_leg{leg}"] - front)
 out["verify_stage_per_item_exact"] = out["agg_verify_per_item_exact"] - front
+# leg 1 under each item Miller kernel: 0 = affine arguments
+# and the product kernel, 1 = Jacobian arguments, 2 = Jacobian arguments and
+# the product across the wave (every lane multiplies in each of six rounds,
+# where the product kernel's tree does 63 multiplications per chunk)
+assert lib.hbls_set_aggrlc_sigleg(1) == 1
+for lvl in (0, 1, 2):
+    assert lib.hbls_set_aggrlc_miller(lvl) == 1
+    out[f"agg_verify_per_item_combined_leg1_miller{lvl}"] = count(
+        lambda: lib.hbls_batch_agg_verify(com, bm * nb, sig * nb, msg * nb, len(msg),
+                                          nb, bres)) // nb
+    assert list(bres) == [1] * nb, lvl
+    out[f"verify_stage_per_item_combined_leg1_miller{lvl}"] = (
+        out[f"agg_verify_per_item_combined_leg1_miller{lvl}"] - front)
+lib.hbls_set_aggrlc_miller(-1)
 lib.hbls_set_aggrlc_sigleg(-1)
 lib.hbls_set_agg_verify_mode(-1)
 lib.hbls_set_aggrlc_threshold(-1)
