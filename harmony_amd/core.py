@@ -4,6 +4,7 @@ the C-ABI in include/hbls.h).
 Fails loudly if the library is missing or no AMD GPU is present: there is NO
 CPU fallback here.  The CPU oracle under oracle/ is test infrastructure only.
 """
+import contextlib
 import ctypes
 import os
 
@@ -125,6 +126,7 @@ def _load():
     lib.hbls_set_aggrlc_miller.argtypes = [ctypes.c_int]
     lib.hbls_aggrlc_probe.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
                                       ctypes.c_char_p]
+    lib.hbls_aggrlc_switch_value.argtypes = [ctypes.c_int, ctypes.c_size_t]
     lib.hbls_last_host_ns.restype = ctypes.c_uint64
     lib.hbls_last_host_ns.argtypes = [ctypes.c_int]
     u64p, u32p, i32p = (ctypes.POINTER(t) for t in
@@ -293,11 +295,47 @@ def set_aggrlc_chunkleg(kernel: int):
 
 
 def set_aggrlc_miller(level: int):
-    """Miller kernel of the chunk-level leg's items: 0 =
-    affine arguments and a product kernel of its own; 1 = Jacobian arguments,
-    no inversion; 2 = that, and the chunk product inside the Miller kernel;
-    -1 restores the default.  Verdicts and stats do not depend on it."""
+    """level of the chunk-level leg's item kernel, k_aggrlc_item (DESIGN.md
+    §4m, §4n): 0 = affine arguments and a product kernel of its own; 1 =
+    Jacobian arguments, no inversion; 2 = that, and the chunk product inside
+    the item kernel; -1 restores the default.  Verdicts and stats do not
+    depend on it."""
     _check(_lib.hbls_set_aggrlc_miller(level), "set_aggrlc_miller")
+
+
+_AGGRLC_SETTERS = {"mode": set_agg_verify_mode, "threshold": set_aggrlc_threshold,
+                   "sigleg": set_aggrlc_sigleg, "early": set_aggrlc_early,
+                   "miller": set_aggrlc_miller, "final": set_aggrlc_final,
+                   "chunkleg": set_aggrlc_chunkleg}
+AGGRLC_SWITCHES = ("mode", "final", "sigleg", "early", "miller", "chunkleg")
+
+
+@contextlib.contextmanager
+def aggrlc_switches(**values):
+    """Set the given switches of the combined path (mode, threshold, sigleg,
+    early, miller, final, chunkleg: the arguments of the set_* functions
+    above) for the body of a `with`, and put every one of them back to -1 on
+    the way out, exceptions included.  The switches are process-global, so a
+    missed restore would reach every later call.  If a setter rejects a value
+    nothing stays applied and its BadInputError is raised."""
+    unknown = set(values) - set(_AGGRLC_SETTERS)
+    if unknown:
+        raise TypeError("aggrlc_switches: unknown switch %s" % sorted(unknown))
+    try:
+        for name, v in values.items():
+            _AGGRLC_SETTERS[name](v)
+        yield
+    finally:
+        for name in values:
+            _AGGRLC_SETTERS[name](-1)
+
+
+def aggrlc_switch_value(name: str, batch: int = 0) -> int:
+    """Test hook (needs no GPU): what switch `name` of AGGRLC_SWITCHES resolves
+    to for a call over `batch` items — the value set or read from the
+    environment, with the sigleg and early rules applied to `batch`; -1 is
+    the mode's auto."""
+    return _lib.hbls_aggrlc_switch_value(AGGRLC_SWITCHES.index(name), batch)
 
 
 AGGRLC_PROBE_OPS = {"g1_mul64w": (0, 3 * 48 + 8, 3 * 48),

@@ -55,57 +55,44 @@ DEV void aggrlc_recode64(uint64_t k, uint64_t &mag, uint32_t &neg, uint32_t &top
  * with control flow that depends on the scalar only through the "digit is
  * zero" skip — a wave of 64 independent scalars runs g1_mul's 63 additions,
  * here 16.  The same group element as g1_mul for every k, p = identity
- * included (g1_add and g1_dbl carry the identity and the doubling case). */
-DEVN void g1_mul64w(g1_t &r, const g1_t &p, uint64_t k) {
-    g1_t tab[8];
+ * included (g1_add and g1_dbl carry the identity and the doubling case).
+ * One body for both groups, over the point type's double, add, negate-y and
+ * set-identity. */
+DEV void pt_dbl(g1_t &r, const g1_t &p) { g1_dbl(r, p); }
+DEV void pt_dbl(g2_t &r, const g2_t &p) { g2_dbl(r, p); }
+DEV void pt_add(g1_t &r, const g1_t &p, const g1_t &q) { g1_add(r, p, q); }
+DEV void pt_add(g2_t &r, const g2_t &p, const g2_t &q) { g2_add(r, p, q); }
+DEV void pt_neg_y(g1_t &p) { fp_neg(p.y, p.y); }
+DEV void pt_neg_y(g2_t &p) { fp2_neg(p.y, p.y); }
+DEV void pt_set_inf(g1_t &p) { g1_set_inf(p); }
+DEV void pt_set_inf(g2_t &p) { g2_set_inf(p); }
+template <typename PT> DEV void pt_mul64w(PT &r, const PT &p, uint64_t k) {
+    PT tab[8];
     tab[0] = p;
-    g1_dbl(tab[1], tab[0]);
-    g1_add(tab[2], tab[1], tab[0]);
-    g1_dbl(tab[3], tab[1]);
-    g1_add(tab[4], tab[3], tab[0]);
-    g1_dbl(tab[5], tab[2]);
-    g1_add(tab[6], tab[5], tab[0]);
-    g1_dbl(tab[7], tab[3]);
+    pt_dbl(tab[1], tab[0]);
+    pt_add(tab[2], tab[1], tab[0]);
+    pt_dbl(tab[3], tab[1]);
+    pt_add(tab[4], tab[3], tab[0]);
+    pt_dbl(tab[5], tab[2]);
+    pt_add(tab[6], tab[5], tab[0]);
+    pt_dbl(tab[7], tab[3]);
     uint64_t mag; uint32_t neg, top;
     aggrlc_recode64(k, mag, neg, top);
-    g1_t acc;
-    if (top) acc = p; else g1_set_inf(acc);
+    PT acc;
+    if (top) acc = p; else pt_set_inf(acc);
     for (int j = 15; j >= 0; j--) {
-        for (int s = 0; s < 4; s++) g1_dbl(acc, acc);
+        for (int s = 0; s < 4; s++) pt_dbl(acc, acc);
         uint32_t m = (uint32_t)(mag >> (4 * j)) & 15u;
         if (m) {
-            g1_t t = tab[m - 1];
-            if ((neg >> j) & 1u) fp_neg(t.y, t.y);
-            g1_add(acc, acc, t);
+            PT t = tab[m - 1];
+            if ((neg >> j) & 1u) pt_neg_y(t);
+            pt_add(acc, acc, t);
         }
     }
     r = acc;
 }
-DEVN void g2_mul64w(g2_t &r, const g2_t &p, uint64_t k) {
-    g2_t tab[8];
-    tab[0] = p;
-    g2_dbl(tab[1], tab[0]);
-    g2_add(tab[2], tab[1], tab[0]);
-    g2_dbl(tab[3], tab[1]);
-    g2_add(tab[4], tab[3], tab[0]);
-    g2_dbl(tab[5], tab[2]);
-    g2_add(tab[6], tab[5], tab[0]);
-    g2_dbl(tab[7], tab[3]);
-    uint64_t mag; uint32_t neg, top;
-    aggrlc_recode64(k, mag, neg, top);
-    g2_t acc;
-    if (top) acc = p; else g2_set_inf(acc);
-    for (int j = 15; j >= 0; j--) {
-        for (int s = 0; s < 4; s++) g2_dbl(acc, acc);
-        uint32_t m = (uint32_t)(mag >> (4 * j)) & 15u;
-        if (m) {
-            g2_t t = tab[m - 1];
-            if ((neg >> j) & 1u) fp2_neg(t.y, t.y);
-            g2_add(acc, acc, t);
-        }
-    }
-    r = acc;
-}
+DEVN void g1_mul64w(g1_t &r, const g1_t &p, uint64_t k) { pt_mul64w(r, p, k); }
+DEVN void g2_mul64w(g2_t &r, const g2_t &p, uint64_t k) { pt_mul64w(r, p, k); }
 
 /* f = f_{|z|,Q}(P): one leg of miller_loop2, the same homogeneous steps */
 DEVN void miller_loop1_h(fp12_t &f, const g2aff_t &Q, const g1aff_t &P) {
@@ -124,19 +111,60 @@ DEVN void miller_loop1_h(fp12_t &f, const g2aff_t &Q, const g1aff_t &P) {
     }
 }
 
+/* -G1, affine: the fixed G1 argument of every signature leg */
+DEV void aggrlc_neg_g1(g1aff_t &P) {
+    fp_load(P.x, BLS_G1_X);
+    fp_t gy;
+    fp_load(gy, BLS_G1_Y);
+    fp_neg(P.y, gy);
+}
+
 /* p2[k] = 2^k * (-G1), affine (thread k: k doublings, one inversion): the
  * 64 "keys" whose 8-key subset sums (k_wtab_build_jac) are the fixed-base
  * window table of -G1 */
 __global__ void k_aggrlc_pow2(g1aff_t *p2) {
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= 64) return;
-    g1_t base, p;
-    fp_load(base.x, BLS_G1_X); fp_load(base.y, BLS_G1_Y); fp_one(base.z);
-    g1_neg(p, base);
+    g1aff_t n;
+    aggrlc_neg_g1(n);
+    g1_t p;
+    p.x = n.x; p.y = n.y; fp_one(p.z);
     for (int j = 0; j < k; j++) g1_dbl(p, p);
     g1aff_t a;
     g1_to_affine(a, p);
     p2[k] = a;
+}
+
+/* ---- the verdict rule, in k_verify's guard order — the one place it is
+ * written.  An item is bad input (hash or signature undecodable), decided
+ * without a pairing (identity key sum or identity signature: the herumi
+ * verdict, accepted only when both are), or eligible for the combined check;
+ * `verdict` is what results[i] gets (for an eligible item the 1 that stands
+ * unless its chunk fails and is re-checked).
+ * pub == nullptr: the key sum does not exist yet (the hoisted schedule, ahead
+ * of the mask kernel).  An identity signature then stays open, verdict
+ * untouched, and a real one is eligible for now; the same function with the
+ * key sum at hand closes both. */
+enum { AGGRLC_CLS_BAD = 0, AGGRLC_CLS_DECIDED, AGGRLC_CLS_ELIGIBLE, AGGRLC_CLS_OPEN };
+DEV int aggrlc_classify(int32_t hm_ok, int32_t sig_flag, const g1_t *pub, int32_t &verdict) {
+    if (!hm_ok || sig_flag == 0) { verdict = HBLS_ERR_BADINPUT; return AGGRLC_CLS_BAD; }
+    bool sig_inf = sig_flag == 2;
+    if (!pub) {
+        if (sig_inf) return AGGRLC_CLS_OPEN;
+    } else {
+        bool pub_inf = g1_is_inf(*pub);
+        if (pub_inf || sig_inf) {
+            verdict = (pub_inf && sig_inf) ? 1 : 0;   /* herumi edge */
+            return AGGRLC_CLS_DECIDED;
+        }
+    }
+    verdict = 1;
+    return AGGRLC_CLS_ELIGIBLE;
+}
+/* the item's scalar: a drawn zero would drop the item from the product */
+DEV uint64_t aggrlc_scalar(const uint64_t *scalars, size_t i) {
+    uint64_t r = scalars[i];
+    return r ? r : 1;
 }
 
 /* thread per item: verify_pairing up to (and without) the final
@@ -153,17 +181,11 @@ __global__ void k_aggrlc_miller(const g1_t *aggpubs, const g2_t *hms, const g2af
     fp12_t f;
     fp12_one(f);
     elig[i] = 0;
-    if (!hm_ok[i] || sig_flags[i] == 0) {
-        results[i] = HBLS_ERR_BADINPUT; F[i] = f; return;
-    }
-    bool sig_inf = sig_flags[i] == 2;
-    bool pub_inf = g1_is_inf(aggpubs[i]);
-    if (pub_inf || sig_inf) {
-        results[i] = (pub_inf && sig_inf) ? 1 : 0;   /* herumi edge */
-        F[i] = f; return;
-    }
-    uint64_t r = scalars[i];
-    if (r == 0) r = 1;
+    int32_t v = 0;
+    int cls = aggrlc_classify(hm_ok[i], sig_flags[i], aggpubs + i, v);
+    results[i] = v;
+    if (cls != AGGRLC_CLS_ELIGIBLE) { F[i] = f; return; }
+    uint64_t r = aggrlc_scalar(scalars, i);
     g1_t A, C;
     g1_mul64w(A, aggpubs[i], r);
     g1_set_inf(C);
@@ -194,23 +216,22 @@ __global__ void k_aggrlc_miller(const g1_t *aggpubs, const g2_t *hms, const g2af
     miller_loop2(f, ha, pa, sigs[i], ca);
     F[i] = f;
     elig[i] = 1;
-    results[i] = 1;      /* stands unless the chunk fails and is re-checked */
 }
 
 /* elig value of the hoisted schedule only (DESIGN.md §4l), between
- * k_aggrlc_sigscale<true> and k_aggrlc_miller1<true>: an identity signature
+ * k_aggrlc_sigscale<true> and k_aggrlc_item<true, *>: an identity signature
  * whose verdict waits for the key sum.  No later kernel sees it. */
 #define AGGRLC_ELIG_OPEN 3
 
-/* chunk-level signature leg, step 1 — thread per item: k_aggrlc_miller's
- * classification in its guard order (aggpubs[i] is read for g1_is_inf only),
- * then B_i = r_i*sig_i, Jacobian.  Classified items get elig 0 and B_i =
- * identity, so the chunk sum needs no flags.
+/* chunk-level signature leg, step 1 — thread per item: the classification
+ * (aggpubs[i] is read for g1_is_inf only), then B_i = r_i*sig_i, Jacobian.
+ * Classified items get elig 0 and B_i = identity, so the chunk sum needs no
+ * flags.
  * HOISTED: the launch runs ahead of the mask kernel, so aggpubs does not
- * exist yet and is not read.  The guard order stays, minus the key-sum test:
- * an identity signature is left open (AGGRLC_ELIG_OPEN, B_i = identity), an
- * item with a real signature is scaled whatever its key sum will be, and
- * k_aggrlc_miller1<true> finishes both once it has the key sums. */
+ * exist yet and is not read: an identity signature is left open
+ * (AGGRLC_ELIG_OPEN, B_i = identity), an item with a real signature is scaled
+ * whatever its key sum will be, and k_aggrlc_item<true, *> finishes both once
+ * it has the key sums. */
 template <bool HOISTED>
 __global__ void k_aggrlc_sigscale(const g1_t *aggpubs, const g2aff_t *sigs,
                                   const int32_t *sig_flags, const int32_t *hm_ok,
@@ -220,28 +241,18 @@ __global__ void k_aggrlc_sigscale(const g1_t *aggpubs, const g2aff_t *sigs,
     if (i >= batch) return;
     g2_t b;
     g2_set_inf(b);
-    elig[i] = 0;
-    if (!hm_ok[i] || sig_flags[i] == 0) {
-        results[i] = HBLS_ERR_BADINPUT; B[i] = b; return;
+    int32_t v = 0;
+    int cls = aggrlc_classify(hm_ok[i], sig_flags[i], HOISTED ? nullptr : aggpubs + i, v);
+    if (cls != AGGRLC_CLS_OPEN) results[i] = v;
+    if (cls != AGGRLC_CLS_ELIGIBLE) {
+        elig[i] = cls == AGGRLC_CLS_OPEN ? AGGRLC_ELIG_OPEN : 0;
+        B[i] = b; return;
     }
-    bool sig_inf = sig_flags[i] == 2;
-    if (HOISTED) {
-        if (sig_inf) { elig[i] = AGGRLC_ELIG_OPEN; B[i] = b; return; }
-    } else {
-        bool pub_inf = g1_is_inf(aggpubs[i]);
-        if (pub_inf || sig_inf) {
-            results[i] = (pub_inf && sig_inf) ? 1 : 0;   /* herumi edge */
-            B[i] = b; return;
-        }
-    }
-    uint64_t r = scalars[i];
-    if (r == 0) r = 1;
     g2_t s;
     g2_from_affine(s, sigs[i]);
-    g2_mul64w(b, s, r);
+    g2_mul64w(b, s, aggrlc_scalar(scalars, i));
     B[i] = b;
     elig[i] = 1;
-    results[i] = 1;      /* stands unless the chunk fails and is re-checked */
 }
 
 /* step 2 — one block per chunk (k_rlc_chunk_sum's shape): LDS tree over the
@@ -283,72 +294,6 @@ __global__ void __launch_bounds__(AGGRLC_CHUNK) k_aggrlc_sigsum(
             sflag[c] = 1;
         }
     }
-}
-
-/* step 3 — batch + nchunks threads, one Miller leg each.  Thread i < batch
- * with elig 1: f(H_i; r_i*aggpk_i), or elig 2 when the scaled key sum is the
- * identity (as k_aggrlc_miller).  Thread batch + c: the chunk entry
- * f(S_c; -G1), one when sflag[c] is 0.  Both kinds meet in one call of the
- * loop, so the block that holds the boundary does not run it twice.
- * HOISTED (launched with nchunks = 0: the chunk entries have a kernel of
- * their own, k_aggrlc_chunkleg): the item threads first finish what
- * k_aggrlc_sigscale<true> could not decide without the key sums.  An open
- * identity signature gets the herumi verdict.  An eligible item whose key
- * sum is the identity is rejected as k_aggrlc_sigscale<false> would have
- * done, and since its B_i is already inside S_c it marks the chunk dirty
- * (every writer stores the same value) for the repair launches. */
-template <bool HOISTED>
-__global__ void k_aggrlc_miller1(const g1_t *aggpubs, const g2_t *hms,
-                                 const uint64_t *scalars, const g2aff_t *S,
-                                 const int32_t *sflag, fp12_t *F, int32_t *elig,
-                                 int32_t *results, int batch, int nchunks,
-                                 int32_t *dirty) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)batch + (size_t)nchunks) return;
-    fp12_t f;
-    g2aff_t Q;
-    g1aff_t P;
-    bool run = false;
-    if (i < (size_t)batch) {
-        if (HOISTED) {
-            int32_t e = elig[i];
-            if (e == AGGRLC_ELIG_OPEN) {
-                results[i] = g1_is_inf(aggpubs[i]) ? 1 : 0;      /* herumi edge */
-                elig[i] = 0;
-            } else if (e == 1 && g1_is_inf(aggpubs[i])) {
-                results[i] = 0;
-                elig[i] = 0;
-                dirty[i / AGGRLC_CHUNK] = 1;
-            }
-        }
-        if (elig[i] == 1) {
-            uint64_t r = scalars[i];
-            if (r == 0) r = 1;
-            g1_t A;
-            g1_mul64w(A, aggpubs[i], r);
-            if (g1_is_inf(A)) {
-                elig[i] = 2; results[i] = 0;
-            } else {
-                g1_to_affine(P, A);
-                g2_t hmc = hms[i];
-                g2_to_affine(Q, hmc);
-                run = true;
-            }
-        }
-    } else {
-        size_t c = i - (size_t)batch;
-        if (sflag[c]) {
-            Q = S[c];
-            fp_load(P.x, BLS_G1_X);
-            fp_t gy;
-            fp_load(gy, BLS_G1_Y);
-            fp_neg(P.y, gy);
-            run = true;
-        }
-    }
-    if (run) miller_loop1_h(f, Q, P);
-    else fp12_one(f);
-    F[i] = f;
 }
 
 /* product of f over the 64 lanes of a wave, without LDS: six butterfly
@@ -398,90 +343,120 @@ DEVN void fp12_wave_prod(fp12_t &f) {
     f = a.v;
 }
 
-/* k_aggrlc_miller1 without the two inversions at its head (DESIGN.md §4m):
- * an item thread hands r_i*aggpk_i and H_i to miller_loop1_hj as they are,
- * Jacobian.  A hash point with Z = 0 — which hashing cannot produce — is
- * treated like an identity key sum: elig 2, so that no input skips its
- * pairing.  The chunk entries (affine S_c, -G1) keep miller_loop1_h, so
- * unlike k_aggrlc_miller1 the two kinds do not meet in one call of a loop:
- * the not-hoisted instantiations carry both loops, and in <false, false> the
- * one wave that holds the last items and the first entries (batch not a
- * multiple of 64) runs them one after the other — one wave, at the kernel's
- * tail.  <false, true> has no such wave: its entries have blocks of their own.
- * FUSED: the block is the chunk.  Blocks 0..nchunks-1 hold the items, lane l
- * of block c is item 64c + l, and no thread leaves before the product: lanes
- * past the batch, classified items and items this kernel demotes hold one.
- * The product is taken across the wave (fp12_wave_prod) and lane 0 stores
- * FC[c], ccnt[c] and cforce[c] with k_aggrlc_chunk_prod's meaning; F does not
- * exist.  Blocks from nchunks on, present in the launch when the chunk
- * entries are not hoisted, are the chunk entries: thread per chunk, FX[c]. */
-template <bool HOISTED, bool FUSED>
-__global__ void k_aggrlc_miller1j(const g1_t *aggpubs, const g2_t *hms,
-                                  const uint64_t *scalars, const g2aff_t *S,
-                                  const int32_t *sflag, fp12_t *F, int32_t *elig,
-                                  int32_t *results, int batch, int nchunks,
-                                  int32_t *dirty, fp12_t *FC, int32_t *ccnt,
-                                  int32_t *cforce) {
-    const bool item_block = !FUSED || (int)blockIdx.x < nchunks;
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    size_t c = 0;
-    bool is_item, is_entry;
-    if (FUSED) {
-        is_item = item_block && i < (size_t)batch;
-        c = i - (size_t)nchunks * blockDim.x;
-        is_entry = !HOISTED && !item_block && c < (size_t)nchunks;
-        if (!item_block && !is_entry) return;
-    } else {
-        if (i >= (size_t)batch + (size_t)nchunks) return;
-        is_item = i < (size_t)batch;
-        is_entry = !is_item;
-        c = i - (size_t)batch;
+/* the chunk entry f(S_c; -G1).  As arguments for miller_loop1_h: false, and
+ * nothing written, when the chunk sum is the identity (sflag[c] == 0) and the
+ * entry is one.  As a value: the loop run, or one. */
+DEV bool aggrlc_entry_args(const g2aff_t *S, const int32_t *sflag, size_t c,
+                           g2aff_t &Q, g1aff_t &P) {
+    if (!sflag[c]) return false;
+    Q = S[c];
+    aggrlc_neg_g1(P);
+    return true;
+}
+DEV void aggrlc_chunk_entry(fp12_t &f, const g2aff_t *S, const int32_t *sflag, size_t c) {
+    g2aff_t Q;
+    g1aff_t P;
+    if (aggrlc_entry_args(S, sflag, c, Q, P)) miller_loop1_h(f, Q, P);
+    else fp12_one(f);
+}
+
+/* what an item thread of k_aggrlc_item does ahead of its loop; returns the
+ * item's elig, and with 1 also A = r_i*aggpk_i.
+ * HOISTED: first what k_aggrlc_sigscale<true> left for the key sum — the same
+ * rule, now with it.  An open identity signature gets the herumi verdict.  An
+ * eligible item whose key sum is the identity is rejected, and since its B_i
+ * is already inside S_c it marks the chunk dirty (every writer stores the
+ * same value) for the repair launches.
+ * Then the scaled key sum; the identity there is elig 2, as in k_aggrlc_miller. */
+template <bool HOISTED>
+DEV int32_t aggrlc_item_prologue(const g1_t *aggpubs, const uint64_t *scalars, int32_t *elig,
+                                 int32_t *results, int32_t *dirty, size_t i, g1_t &A) {
+    int32_t e = elig[i];
+    if (HOISTED && (e == AGGRLC_ELIG_OPEN || e == 1)) {
+        int32_t v;
+        int cls = aggrlc_classify(1, e == AGGRLC_ELIG_OPEN ? 2 : 1, aggpubs + i, v);
+        if (cls == AGGRLC_CLS_DECIDED) {
+            results[i] = v;
+            elig[i] = 0;
+            if (e == 1) dirty[i / AGGRLC_CHUNK] = 1;
+            e = 0;
+        }
     }
+    if (e != 1) return e;
+    g1_mul64w(A, aggpubs[i], aggrlc_scalar(scalars, i));
+    if (g1_is_inf(A)) { elig[i] = e = 2; results[i] = 0; }
+    return e;
+}
+
+/* step 3 — one Miller leg per thread: item i with elig 1 computes
+ * f(H_i; r_i*aggpk_i), the entry thread of chunk c f(S_c; -G1) into FX[c].
+ * Not HOISTED, the entries ride behind the items in the same launch; HOISTED,
+ * they have a kernel of their own (k_aggrlc_chunkleg) and no threads here.
+ * LEVEL 0: batch + nchunks threads; the arguments go to affine and both
+ * kinds meet in one call of miller_loop1_h, so the block that holds the
+ * boundary does not run it twice.  F[i] for k_aggrlc_chunk_prod.
+ * LEVEL 1 (DESIGN.md §4m): no inversion — r_i*aggpk_i and H_i go to
+ * miller_loop1_hj as they are, Jacobian.  A hash point with Z = 0, which
+ * hashing cannot produce, is elig 2 like an identity key sum, so that no
+ * input skips its pairing.  The entries (affine S_c, -G1) keep
+ * miller_loop1_h: the one wave that holds the last items and the first
+ * entries runs the two loops one after the other.
+ * LEVEL 2: that, and the block is the chunk: lane l of block c < nchunks is
+ * item 64c + l, and no thread leaves before the product — lanes past the
+ * batch, classified and demoted items hold one.  fp12_wave_prod takes it and
+ * lane 0 stores FC[c], ccnt[c], cforce[c] with k_aggrlc_chunk_prod's meaning;
+ * F does not exist.  The entries, when not hoisted, are the blocks from
+ * nchunks on, thread per chunk. */
+template <bool HOISTED, int LEVEL>
+__global__ void k_aggrlc_item(const g1_t *aggpubs, const g2_t *hms, const uint64_t *scalars,
+                              const g2aff_t *S, const int32_t *sflag, fp12_t *F, fp12_t *FX,
+                              int32_t *elig, int32_t *results, int batch, int nchunks,
+                              int32_t *dirty, fp12_t *FC, int32_t *ccnt, int32_t *cforce) {
+    constexpr bool FUSED = LEVEL == 2;
+    /* the entry threads, when there are any, start at this thread index */
+    const size_t first_entry = FUSED ? (size_t)nchunks * blockDim.x : (size_t)batch;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, c = i - first_entry;
+    const bool is_entry = !HOISTED && i >= first_entry;
+    const bool is_item = !is_entry && i < (size_t)batch;
+    if (is_entry ? c >= (size_t)nchunks : !FUSED && !is_item) return;
+    fp12_t *dst = is_entry ? FX + c : F + i;    /* one store for both kinds */
     fp12_t f;
+    g2aff_t Q; g1aff_t P;               /* level 0: the one loop's arguments */
     int32_t e = 0;
     bool run = false;
     if (is_item) {
-        e = elig[i];
-        if (HOISTED) {
-            if (e == AGGRLC_ELIG_OPEN) {
-                results[i] = g1_is_inf(aggpubs[i]) ? 1 : 0;      /* herumi edge */
-                elig[i] = e = 0;
-            } else if (e == 1 && g1_is_inf(aggpubs[i])) {
-                results[i] = 0;
-                elig[i] = e = 0;
-                dirty[i / AGGRLC_CHUNK] = 1;
-            }
-        }
+        g1_t A;
+        e = aggrlc_item_prologue<HOISTED>(aggpubs, scalars, elig, results, dirty, i, A);
         if (e == 1) {
-            uint64_t r = scalars[i];
-            if (r == 0) r = 1;
-            g1_t A;
-            g1_mul64w(A, aggpubs[i], r);
-            g2_t hmc = hms[i];
-            if (g1_is_inf(A) || g2_is_inf(hmc)) {
-                elig[i] = e = 2; results[i] = 0;
-            } else {
-                miller_loop1_hj(f, hmc, A);
+            if constexpr (LEVEL == 0) {
+                g1_to_affine(P, A);
+                g2_t hmc = hms[i];
+                g2_to_affine(Q, hmc);
                 run = true;
+            } else {
+                g2_t hmc = hms[i];
+                if (g2_is_inf(hmc)) {
+                    elig[i] = e = 2; results[i] = 0;
+                } else {
+                    miller_loop1_hj(f, hmc, A);
+                    run = true;
+                }
             }
         }
-    } else if (!HOISTED && is_entry) {
-        if (sflag[c]) {
-            g2aff_t Q = S[c];
-            g1aff_t P;
-            fp_load(P.x, BLS_G1_X);
-            fp_t gy;
-            fp_load(gy, BLS_G1_Y);
-            fp_neg(P.y, gy);
-            miller_loop1_h(f, Q, P);
+    } else if (is_entry) {
+        if constexpr (LEVEL == 0) {
+            run = aggrlc_entry_args(S, sflag, c, Q, P);
+        } else {
+            aggrlc_chunk_entry(f, S, sflag, c);
             run = true;
         }
     }
+    if constexpr (LEVEL == 0) {
+        if (run) miller_loop1_h(f, Q, P);
+    }
     if (!run) fp12_one(f);
-    if (!FUSED) {
-        F[i] = f;
-    } else if (!item_block) {
-        F[c] = f;                       /* the chunk entries' buffer, FX */
+    if (!FUSED || is_entry) {
+        *dst = f;
     } else {
         fp12_wave_prod(f);
         unsigned long long any = __ballot(e != 0), force = __ballot(e == 2);
@@ -503,7 +478,7 @@ __global__ void k_aggrlc_chunk_fold(fp12_t *FC, const fp12_t *FX, int nchunks) {
     FC[c] = a;
 }
 
-/* the chunk entries of k_aggrlc_miller1 as a kernel of their own — thread
+/* the chunk entries of k_aggrlc_item as a kernel of their own — thread
  * per chunk: FX[c] = f(S_c; -G1), one when sflag[c] is 0.  The hoisted
  * schedule runs it on a side stream beside the mask kernel, where its 64
  * long waves take slots the short mask blocks leave, instead of behind a
@@ -515,17 +490,7 @@ __global__ void k_aggrlc_chunkleg(const g2aff_t *S, const int32_t *sflag,
     if (c >= nchunks) return;
     if (dirty && !dirty[c]) return;
     fp12_t f;
-    if (sflag[c]) {
-        g2aff_t Q = S[c];
-        g1aff_t P;
-        fp_load(P.x, BLS_G1_X);
-        fp_t gy;
-        fp_load(gy, BLS_G1_Y);
-        fp_neg(P.y, gy);
-        miller_loop1_h(f, Q, P);
-    } else {
-        fp12_one(f);
-    }
+    aggrlc_chunk_entry(f, S, sflag, (size_t)c);
     FX[c] = f;
 }
 
@@ -586,10 +551,10 @@ __global__ void __launch_bounds__(ITEMS * CV_LANES) k_aggrlc_chunkleg_coop(
             fp_load(Q.y.a, BLS_G2_YA); fp_load(Q.y.b, BLS_G2_YB);
         }
         lds_st(A + (CV_Q1), Q.x); lds_st(A + (CV_Q1 + 1), Q.y);
+        g1aff_t n;
+        aggrlc_neg_g1(n);
         fp2_t p;
-        fp_t gy;
-        fp_load(p.a, BLS_G1_X); fp_load(gy, BLS_G1_Y);
-        fp_neg(p.b, gy);                      /* -G1 */
+        p.a = n.x; p.b = n.y;
         lds_st(A + (CV_PP), p);
     }
     __syncthreads();
@@ -708,7 +673,11 @@ __global__ void k_verify_sel(const uint32_t *sel, int nsel, const g1_t *aggpubs,
     if (j >= nsel) return;
     uint32_t i = sel[j];
     if (i >= (uint32_t)batch) return;
-    if (!hm_ok[i] || sig_flags[i] == 0) { results[i] = HBLS_ERR_BADINPUT; return; }
+    /* the rule's first guard; verify_pairing holds the rest of it */
+    int32_t v;
+    if (aggrlc_classify(hm_ok[i], sig_flags[i], nullptr, v) == AGGRLC_CLS_BAD) {
+        results[i] = v; return;
+    }
     g2aff_t dummy;
     bool sig_inf = sig_flags[i] == 2;
     results[i] = verify_pairing(aggpubs[i], hms[i], sig_inf ? dummy : sigs[i], sig_inf);
@@ -727,135 +696,93 @@ static void aggrlc_stats_reset(void) {
 }
 extern "C" int hbls_aggrlc_chunk_size(void) { return AGGRLC_CHUNK; }
 
-static int g_agg_verify_mode = -2;      /* -2: read env on first use */
 /* smallest batch the auto mode sends to the combined path: the smallest one
  * measured, with the cooperative tail (DESIGN.md §4h; 131072 with the
  * one-lane tail, §4e) */
 #define AGGRLC_DEFAULT_THRESHOLD 16384
 static int g_aggrlc_threshold = AGGRLC_DEFAULT_THRESHOLD;
-static int agg_verify_mode(void) {
-    if (g_agg_verify_mode == -2) {
-        const char *e = getenv("HBLS_AGG_VERIFY_MODE");
-        int m = e ? atoi(e) : -1;
-        g_agg_verify_mode = (m == 0 || m == 1) ? m : -1;
-    }
-    return g_agg_verify_mode;
-}
-extern "C" int hbls_set_agg_verify_mode(int mode) {
-    if (mode < -1 || mode > 1) return HBLS_ERR_BADINPUT;
-    g_agg_verify_mode = mode;
-    return HBLS_OK;
-}
 extern "C" void hbls_set_aggrlc_threshold(int n) {
     g_aggrlc_threshold = n < 0 ? AGGRLC_DEFAULT_THRESHOLD : n;
 }
 
-/* which kernel runs the chunks' final exponentiations: 16 or 8 = cooperative
- * with that many chunks per block, 0 = one lane per chunk (the measured
- * loser at 4096 chunks, DESIGN.md §4h, kept reproducible) */
-#define AGGRLC_FINAL_DEFAULT 16
-static int g_aggrlc_final = -2;         /* -2: read env on first use */
-static int aggrlc_final_kernel(void) {
-    if (g_aggrlc_final == -2) {
-        const char *e = getenv("HBLS_AGGRLC_FINAL");
-        int k = e ? atoi(e) : AGGRLC_FINAL_DEFAULT;
-        g_aggrlc_final = (k == 0 || k == 8 || k == 16) ? k : AGGRLC_FINAL_DEFAULT;
-    }
-    return g_aggrlc_final;
-}
-extern "C" int hbls_set_aggrlc_final(int kernel) {
-    if (kernel == -1) kernel = AGGRLC_FINAL_DEFAULT;
-    if (kernel != 0 && kernel != 8 && kernel != 16) return HBLS_ERR_BADINPUT;
-    g_aggrlc_final = kernel;
-    return HBLS_OK;
-}
-/* where the signature leg is paired: 0 = per item (k_aggrlc_miller, two
- * legs), 1 = once per chunk (k_aggrlc_sigscale, k_aggrlc_sigsum,
- * k_aggrlc_miller1).  The default rule is §4e's threshold rule on the
- * per-call sweep of DESIGN.md §4k: leg 1 from the smallest measured batch at
- * which it wins the wall clock at every larger one. */
+/* ---- the switches of the combined path, process-global.  Each has an
+ * environment variable read on first use, a default, the values it accepts,
+ * and a setter that takes those, or -1 for the default.  A default of -1 is
+ * a setting too: "auto" for the mode, and for sigleg and early "the rule", 1
+ * from the smallest measured batch at which the variant stops losing the wall
+ * clock (DESIGN.md §4k, §4l: for early the largest one measured).
+ *   mode      0 exact, 1 combined from the threshold up, auto: aggrlc_wanted
+ *   final     the chunks' final exponentiations: 16 or 8 = cooperative, that
+ *             many chunks per block; 0 = one lane per chunk (§4h's measured
+ *             loser at 4096 chunks, kept reproducible)
+ *   sigleg    the signature leg: 0 = per item (k_aggrlc_miller, two legs),
+ *             1 = per chunk (k_aggrlc_sigscale, _sigsum, _item)
+ *   early     the chunk-level leg (§4l): 0 = inside the item kernel, behind
+ *             the items; 1 = hoisted (AggrlcEarly)
+ *   miller    the item kernel's level (§4m): 0 = affine arguments, F to
+ *             memory, k_aggrlc_chunk_prod; 1 = Jacobian arguments; 2 = that
+ *             and the product in the kernel (k_aggrlc_chunk_fold); default
+ *             the highest level that won §4m's sweep.  The variable must be
+ *             exactly one digit; anything else, a typo included, is the default
+ *   chunkleg  the hoisted chunk legs: 16 = k_aggrlc_chunkleg_coop; 0 = one
+ *             lane per chunk (k_aggrlc_chunkleg, which outlasts the mask
+ *             kernel at the benchmark's size, §4l, kept reproducible).  The
+ *             repair launch is always the one-lane kernel */
 #define AGGRLC_SIGLEG_MIN_BATCH 16384
-static int g_aggrlc_sigleg = -2;        /* -2: read env on first use; -1: the rule */
-static int aggrlc_sigleg(size_t batch) {
-    if (g_aggrlc_sigleg == -2) {
-        const char *e = getenv("HBLS_AGGRLC_SIGLEG");
-        int k = e ? atoi(e) : -1;
-        g_aggrlc_sigleg = (k == 0 || k == 1) ? k : -1;
-    }
-    if (g_aggrlc_sigleg >= 0) return g_aggrlc_sigleg;
-    return batch >= AGGRLC_SIGLEG_MIN_BATCH ? 1 : 0;
-}
-extern "C" int hbls_set_aggrlc_sigleg(int leg) {
-    if (leg < -1 || leg > 1) return HBLS_ERR_BADINPUT;
-    g_aggrlc_sigleg = leg;
-    return HBLS_OK;
-}
-
-/* when the chunk-level leg is paired (DESIGN.md §4l): 0 = inside the Miller
- * kernel, behind the items; 1 = hoisted (AggrlcEarly below).  The default
- * rule: hoisted from the smallest batch of the per-call sweep of §4l from
- * which it does not lose the wall clock beyond the spread.  That is the
- * largest one measured: below it the chunk entries ride in the Miller grid's
- * partial last round for nothing, and hoisting only slows the mask kernel. */
 #define AGGRLC_EARLY_MIN_BATCH 262144
-static int g_aggrlc_early = -2;         /* -2: read env on first use; -1: the rule */
-static int aggrlc_early(size_t batch) {
-    if (g_aggrlc_early == -2) {
-        const char *e = getenv("HBLS_AGGRLC_EARLY");
-        int k = e ? atoi(e) : -1;
-        g_aggrlc_early = (k == 0 || k == 1) ? k : -1;
+enum { AGGRLC_SW_MODE = 0, AGGRLC_SW_FINAL, AGGRLC_SW_SIGLEG, AGGRLC_SW_EARLY,
+       AGGRLC_SW_MILLER, AGGRLC_SW_CHUNKLEG, AGGRLC_SW_N };
+struct AggrlcSwitch {
+    const char *env;
+    int dflt, accepted[3], n_accepted;
+    bool one_digit;         /* the variable is one digit character, no atoi */
+    size_t rule_min_batch;  /* dflt == -1: 1 from this batch size on, 0 = no rule */
+    int value;              /* -2: read env on first use */
+    bool accepts(int v) const {
+        for (int k = 0; k < n_accepted; k++)
+            if (accepted[k] == v) return true;
+        return false;
     }
-    if (g_aggrlc_early >= 0) return g_aggrlc_early;
-    return batch >= AGGRLC_EARLY_MIN_BATCH ? 1 : 0;
+};
+static AggrlcSwitch g_aggrlc_sw[AGGRLC_SW_N] = {
+    { "HBLS_AGG_VERIFY_MODE", -1, { 0, 1 }, 2, false, 0, -2 },
+    { "HBLS_AGGRLC_FINAL", 16, { 0, 8, 16 }, 3, false, 0, -2 },
+    { "HBLS_AGGRLC_SIGLEG", -1, { 0, 1 }, 2, false, AGGRLC_SIGLEG_MIN_BATCH, -2 },
+    { "HBLS_AGGRLC_EARLY", -1, { 0, 1 }, 2, false, AGGRLC_EARLY_MIN_BATCH, -2 },
+    { "HBLS_AGGRLC_MILLER", 2, { 0, 1, 2 }, 3, true, 0, -2 },
+    { "HBLS_AGGRLC_CHUNKLEG", 16, { 0, 16 }, 2, false, 0, -2 },
+};
+/* the switch's value for a call over `batch` items */
+static int aggrlc_switch(int which, size_t batch) {
+    AggrlcSwitch &s = g_aggrlc_sw[which];
+    if (s.value == -2) {
+        const char *e = getenv(s.env);
+        int v = s.dflt;
+        if (e && s.one_digit) v = (e[0] >= '0' && e[0] <= '9' && e[1] == '\0') ? e[0] - '0' : -2;
+        else if (e) v = atoi(e);
+        s.value = s.accepts(v) ? v : s.dflt;
+    }
+    if (s.value >= 0 || !s.rule_min_batch) return s.value;
+    return batch >= s.rule_min_batch ? 1 : 0;
 }
-extern "C" int hbls_set_aggrlc_early(int early) {
-    if (early < -1 || early > 1) return HBLS_ERR_BADINPUT;
-    g_aggrlc_early = early;
+static int aggrlc_switch_set(int which, int v) {
+    AggrlcSwitch &s = g_aggrlc_sw[which];
+    if (v == -1) v = s.dflt;
+    else if (!s.accepts(v)) return HBLS_ERR_BADINPUT;
+    s.value = v;
     return HBLS_OK;
 }
-
-/* which Miller kernel runs leg 1's items (DESIGN.md §4m): 0 = k_aggrlc_miller1
- * (affine arguments, F to memory, k_aggrlc_chunk_prod); 1 = Jacobian
- * arguments, no inversion (k_aggrlc_miller1j); 2 = that, and the chunk
- * product inside the kernel (no F, k_aggrlc_chunk_fold).  The default is the
- * highest level that won the per-call sweep of §4m by the project's rule. */
-#define AGGRLC_MILLER_DEFAULT 2
-static int g_aggrlc_miller = -2;        /* -2: read env on first use */
-static int aggrlc_miller_level(void) {
-    if (g_aggrlc_miller == -2) {
-        const char *e = getenv("HBLS_AGGRLC_MILLER");
-        /* exactly "0", "1" or "2": anything else, a typo included, is the default */
-        bool digit = e && e[0] >= '0' && e[0] <= '2' && e[1] == '\0';
-        g_aggrlc_miller = digit ? e[0] - '0' : AGGRLC_MILLER_DEFAULT;
-    }
-    return g_aggrlc_miller;
-}
-extern "C" int hbls_set_aggrlc_miller(int level) {
-    if (level < -1 || level > 2) return HBLS_ERR_BADINPUT;
-    g_aggrlc_miller = level == -1 ? AGGRLC_MILLER_DEFAULT : level;
-    return HBLS_OK;
-}
-
-/* which kernel runs the hoisted chunk legs: 16 = four lanes per chunk, 16
- * chunks per block (k_aggrlc_chunkleg_coop); 0 = one lane per chunk
- * (k_aggrlc_chunkleg, which outlasts the mask kernel at the benchmark's size,
- * DESIGN.md §4l, kept reproducible).  The repair launch is always the
- * one-lane kernel: its clean chunks return at once. */
-#define AGGRLC_CHUNKLEG_DEFAULT 16
-static int g_aggrlc_chunkleg = -2;      /* -2: read env on first use */
-static int aggrlc_chunkleg_kernel(void) {
-    if (g_aggrlc_chunkleg == -2) {
-        const char *e = getenv("HBLS_AGGRLC_CHUNKLEG");
-        int k = e ? atoi(e) : AGGRLC_CHUNKLEG_DEFAULT;
-        g_aggrlc_chunkleg = (k == 0 || k == 16) ? k : AGGRLC_CHUNKLEG_DEFAULT;
-    }
-    return g_aggrlc_chunkleg;
-}
-extern "C" int hbls_set_aggrlc_chunkleg(int kernel) {
-    if (kernel == -1) kernel = AGGRLC_CHUNKLEG_DEFAULT;
-    if (kernel != 0 && kernel != 16) return HBLS_ERR_BADINPUT;
-    g_aggrlc_chunkleg = kernel;
-    return HBLS_OK;
+extern "C" int hbls_set_agg_verify_mode(int v) { return aggrlc_switch_set(AGGRLC_SW_MODE, v); }
+extern "C" int hbls_set_aggrlc_final(int v) { return aggrlc_switch_set(AGGRLC_SW_FINAL, v); }
+extern "C" int hbls_set_aggrlc_sigleg(int v) { return aggrlc_switch_set(AGGRLC_SW_SIGLEG, v); }
+extern "C" int hbls_set_aggrlc_early(int v) { return aggrlc_switch_set(AGGRLC_SW_EARLY, v); }
+extern "C" int hbls_set_aggrlc_miller(int v) { return aggrlc_switch_set(AGGRLC_SW_MILLER, v); }
+extern "C" int hbls_set_aggrlc_chunkleg(int v) { return aggrlc_switch_set(AGGRLC_SW_CHUNKLEG, v); }
+/* test hook (not part of the ABI, kept out of include/hbls.h; needs no GPU):
+ * what switch `which` resolves to for a call over `batch` items */
+extern "C" int hbls_aggrlc_switch_value(int which, size_t batch) {
+    if (which < 0 || which >= AGGRLC_SW_N) return HBLS_ERR_BADINPUT;
+    return aggrlc_switch(which, batch);
 }
 
 /* the chunk legs' stream: non-blocking, created on first use and kept for
@@ -880,6 +807,57 @@ static hipStream_t aggrlc_side_stream(void) {
     return g_aggrlc_side_stream;
 }
 
+/* typed pieces of one device allocation, in the order they are taken; each
+ * piece starts on a 256-byte boundary.  Over a null base it only adds up the
+ * size, so one function lays a buffer out for both the allocation and the
+ * pointers. */
+struct Carve {
+    uint8_t *base;
+    size_t used = 0;
+    explicit Carve(void *b) : base((uint8_t *)b) {}
+    template <typename T> T *take(size_t n) {
+        size_t at = used;
+        used += (n * sizeof(T) + 255) & ~(size_t)255;
+        return base ? (T *)(base + at) : nullptr;
+    }
+};
+
+/* the device buffers of a combined call — one allocation, one shape for both
+ * schedules: the hoisted one makes it ahead of the mask kernel (AggrlcEarly),
+ * the other inside aggrlc_verify.  sc, elig: the items' scalars and classes.
+ * The chunk-level leg's, none with the per-item leg: B = r_i*sig_i; S, sflag
+ * the chunk sums; dirty the chunks to repair; FX the entries f(S_c; -G1).
+ * F: the items' f, none at level 2.  FC: the chunk products.  ccnt | cforce |
+ * verdict: one piece, which the host downloads. */
+struct AggrlcBufs {
+    uint64_t *sc;
+    int32_t *elig, *sflag, *dirty, *ccnt, *cforce, *verdict;
+    g2_t *B;
+    g2aff_t *S;
+    fp12_t *FX, *F, *FC;
+    DevBuf buf;         /* after the pointers: its size comes from lay() */
+    AggrlcBufs(size_t batch, size_t nc, const AggrlcPlan &plan) : buf(lay(nullptr, batch, nc, plan)) {
+        if (!buf.err) lay(buf.p, batch, nc, plan);
+    }
+    size_t lay(void *base, size_t batch, size_t nc, const AggrlcPlan &plan) {
+        const size_t nl = plan.leg ? nc : 0;
+        Carve c(base);
+        sc = c.take<uint64_t>(batch);
+        elig = c.take<int32_t>(batch);
+        B = c.take<g2_t>(nl ? batch : 0);
+        S = c.take<g2aff_t>(nl);
+        sflag = c.take<int32_t>(nl);
+        dirty = c.take<int32_t>(nl);
+        FX = c.take<fp12_t>(nl);
+        F = c.take<fp12_t>(plan.level == 2 ? 0 : batch);
+        FC = c.take<fp12_t>(nc);
+        ccnt = c.take<int32_t>(3 * nc);
+        cforce = ccnt + nc;
+        verdict = cforce + nc;
+        return c.used;
+    }
+};
+
 /* ---- the hoisted schedule (DESIGN.md §4l).  The chunk entries depend on
  * the signature chain only (decompress, sigscale, sigsum), the item legs on
  * hash and mask only.  run_agg_verify_pipeline therefore runs the signature
@@ -894,20 +872,12 @@ static hipStream_t aggrlc_side_stream(void) {
  * 2..3 around the chunk-leg kernel on the side stream (slot 8), 4 the
  * scalars' upload. */
 struct AggrlcEarly {
-    size_t batch, nc;
     std::vector<uint64_t> scalars;
-    DevBuf dsc, dB, dS, dFX, delig, dflag;      /* dflag: sflag | dirty */
+    AggrlcBufs bufs;
     EventSet<5> ev;
     bool launched = false;
-    AggrlcEarly(size_t b, size_t n)
-        : batch(b), nc(n), scalars(b), dsc(b * 8), dB(b * sizeof(g2_t)),
-          dS(n * sizeof(g2aff_t)), dFX(n * sizeof(fp12_t)), delig(b * 4), dflag(2 * n * 4) {}
-    bool ok() const {
-        return !dsc.err && !dB.err && !dS.err && !dFX.err && !delig.err && !dflag.err &&
-               ev.err == hipSuccess;
-    }
-    int32_t *sflag() const { return dflag.as<int32_t>(); }
-    int32_t *dirty() const { return dflag.as<int32_t>() + nc; }
+    AggrlcEarly(size_t b, size_t n, const AggrlcPlan &plan) : scalars(b), bufs(b, n, plan) {}
+    bool ok() const { return !bufs.buf.err && ev.err == hipSuccess; }
     ~AggrlcEarly() {
         HostSpan sp(3);
         if (launched) (void)hipStreamSynchronize(g_aggrlc_side_stream);
@@ -915,21 +885,36 @@ struct AggrlcEarly {
 };
 static void aggrlc_early_free(AggrlcEarly *e) { delete e; }
 
+/* the signature chain of the chunk-level leg on the null stream: B_i, then
+ * S_c and sflag[c].  hoisted: ahead of the mask kernel, d_agg not yet there */
+static void launch_aggrlc_sig_chain(bool hoisted, const g1_t *d_agg, const g2aff_t *d_saff,
+                                    const int32_t *d_sflags, const int32_t *d_hok,
+                                    const AggrlcBufs &L, int32_t *d_res, size_t batch, size_t nc) {
+    auto scale = hoisted ? k_aggrlc_sigscale<true> : k_aggrlc_sigscale<false>;
+    hipLaunchKernelGGL(scale, dim3((uint32_t)((batch + 63) / 64)), dim3(64), 0, 0,
+                       d_agg, d_saff, d_sflags, d_hok, (const uint64_t *)L.sc, L.B, L.elig,
+                       d_res, (int)batch);
+    hipLaunchKernelGGL(k_aggrlc_sigsum<false>, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
+                       L.B, (int)batch, (int)nc, L.S, L.sflag,
+                       (const int32_t *)nullptr, (const int32_t *)nullptr);
+}
+
 /* the early part, called by the pipeline between the decompress and the
- * mask launches.  Returns null — nothing launched, nothing written, the call
- * proceeds as without it — unless the combined path with the chunk-level leg
- * is taken, the switch allows it, and the scalars and every buffer are
- * there.  When it returns the state, d_res and elig carry k_aggrlc_sigscale<true>'s
- * classification, S and sflag the chunk sums, and the chunk legs are running
- * on the side stream. */
-static AggrlcEarly *aggrlc_early_begin(const g2aff_t *d_saff, const int32_t *d_sflags,
-                                       const int32_t *d_hok, int32_t *d_res, size_t batch) {
-    if (!aggrlc_wanted(batch) || !aggrlc_sigleg(batch) || !aggrlc_early(batch)) return nullptr;
+ * mask launches.  Returns null and takes the hoisting out of the plan —
+ * nothing launched, nothing written — unless the plan asks for it and the
+ * side stream, the scalars and the buffers are there.  When it returns the
+ * state, d_res and elig carry k_aggrlc_sigscale<true>'s classification, S and
+ * sflag the chunk sums, and the chunk legs are running on the side stream. */
+static AggrlcEarly *aggrlc_early_begin(AggrlcPlan &plan, const g2aff_t *d_saff,
+                                       const int32_t *d_sflags, const int32_t *d_hok,
+                                       int32_t *d_res, size_t batch) {
+    if (!plan.hoisted) return nullptr;
+    plan.hoisted = false;               /* until everything below is in place */
     hipStream_t side = aggrlc_side_stream();
     if (!side) return nullptr;
     size_t nc = (batch + AGGRLC_CHUNK - 1) / AGGRLC_CHUNK;
     uint64_t t_alloc = host_now_ns();
-    AggrlcEarly *st = new (std::nothrow) AggrlcEarly(batch, nc);
+    AggrlcEarly *st = new (std::nothrow) AggrlcEarly(batch, nc, plan);
     g_host_ns[0] += host_now_ns() - t_alloc;
     if (!st) return nullptr;
     if (!st->ok() || !rlc_draw_scalars(st->scalars.data(), batch)) {
@@ -937,9 +922,10 @@ static AggrlcEarly *aggrlc_early_begin(const g2aff_t *d_saff, const int32_t *d_s
         delete st;
         return nullptr;
     }
-    bool good = upload_then_wait(st->dsc.p, st->scalars.data(), batch * 8, st->ev[4]) == hipSuccess;
+    const AggrlcBufs &L = st->bufs;
+    bool good = upload_then_wait(L.sc, st->scalars.data(), batch * 8, st->ev[4]) == hipSuccess;
     st->launched = true;    /* from here on the destructor waits for the side stream */
-    good = good && hipMemsetAsync(st->dirty(), 0, nc * 4, 0) == hipSuccess;
+    good = good && hipMemsetAsync(L.dirty, 0, nc * 4, 0) == hipSuccess;
     if (!good) {
         /* the null stream may hold the upload wait and the memset, which
          * touch nothing the rest of the call reads */
@@ -949,12 +935,7 @@ static AggrlcEarly *aggrlc_early_begin(const g2aff_t *d_saff, const int32_t *d_s
         return nullptr;
     }
     (void)hipEventRecord(st->ev[0], 0);
-    hipLaunchKernelGGL(k_aggrlc_sigscale<true>, dim3((uint32_t)((batch + 63) / 64)), dim3(64), 0, 0,
-                       (const g1_t *)nullptr, d_saff, d_sflags, d_hok, st->dsc.as<uint64_t>(),
-                       st->dB.as<g2_t>(), st->delig.as<int32_t>(), d_res, (int)batch);
-    hipLaunchKernelGGL(k_aggrlc_sigsum<false>, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
-                       st->dB.as<g2_t>(), (int)batch, (int)nc, st->dS.as<g2aff_t>(), st->sflag(),
-                       (const int32_t *)nullptr, (const int32_t *)nullptr);
+    launch_aggrlc_sig_chain(true, nullptr, d_saff, d_sflags, d_hok, L, d_res, batch, nc);
     (void)hipEventRecord(st->ev[1], 0);
     /* the side stream starts behind the chunk sums; its end event is waited
      * for by aggrlc_verify, after the Miller launch */
@@ -968,15 +949,14 @@ static AggrlcEarly *aggrlc_early_begin(const g2aff_t *d_saff, const int32_t *d_s
      * it frees and the legs' blocks, which need more registers and LDS than
      * one retiring mask wave leaves, start late or outlast it (§4l). */
     (void)hipStreamWaitEvent(0, st->ev[2], 0);
-    if (aggrlc_chunkleg_kernel() == 16)
+    if (plan.chunkleg_kernel == 16)
         hipLaunchKernelGGL(k_aggrlc_chunkleg_coop<16>, dim3((uint32_t)((nc + 15) / 16)),
-                           dim3(16 * CV_LANES), 0, side, st->dS.as<g2aff_t>(), st->sflag(),
-                           st->dFX.as<fp12_t>(), (int)nc);
+                           dim3(16 * CV_LANES), 0, side, L.S, L.sflag, L.FX, (int)nc);
     else
         hipLaunchKernelGGL(k_aggrlc_chunkleg, dim3((uint32_t)((nc + 63) / 64)), dim3(64), 0, side,
-                           st->dS.as<g2aff_t>(), st->sflag(), (const int32_t *)nullptr,
-                           st->dFX.as<fp12_t>(), (int)nc);
+                           L.S, L.sflag, (const int32_t *)nullptr, L.FX, (int)nc);
     (void)hipEventRecord(st->ev[3], side);
+    plan.hoisted = true;
     return st;
 }
 
@@ -1046,19 +1026,28 @@ extern "C" int hbls_aggrlc_final_selftest(int nchunks) {
     if (rc != HBLS_OK) return rc;
     if (nchunks < 1 || nchunks > (1 << 20)) return HBLS_ERR_BADINPUT;
     size_t nc = (size_t)nchunks;
-    DevBuf dFC(nc * sizeof(fp12_t)), dcs(2 * nc * 4), dv(3 * nc * 4);
-    if (dFC.err || dcs.err || dv.err) return HBLS_ERR;
-    int32_t *d_ccnt = dcs.as<int32_t>(), *d_cforce = d_ccnt + nc;
-    HIP_OK(hipMemset(dv.p, 0xff, 3 * nc * 4));      /* -1: verdict never stored */
+    fp12_t *d_FC;
+    int32_t *d_ccnt, *d_cforce, *d_v;               /* d_v: a verdict array per kernel */
+    auto lay = [&](void *base) {
+        Carve c(base);
+        d_FC = c.take<fp12_t>(nc);
+        d_ccnt = c.take<int32_t>(nc);
+        d_cforce = c.take<int32_t>(nc);
+        d_v = c.take<int32_t>(3 * nc);
+        return c.used;
+    };
+    DevBuf buf(lay(nullptr));
+    if (buf.err) return HBLS_ERR;
+    lay(buf.p);
+    HIP_OK(hipMemset(d_v, 0xff, 3 * nc * 4));       /* -1: verdict never stored */
     hipLaunchKernelGGL(k_aggrlc_final_fill, dim3((uint32_t)((nc + 63) / 64)), dim3(64), 0, 0,
-                       dFC.as<fp12_t>(), d_ccnt, d_cforce, nchunks);
+                       d_FC, d_ccnt, d_cforce, nchunks);
     const int kernels[3] = { 0, 16, 8 };
     for (int k = 0; k < 3; k++)
-        launch_aggrlc_final(kernels[k], dFC.as<fp12_t>(), d_ccnt, d_cforce,
-                            dv.as<int32_t>() + k * nc, nchunks);
+        launch_aggrlc_final(kernels[k], d_FC, d_ccnt, d_cforce, d_v + k * nc, nchunks);
     HIP_OK(hipGetLastError());
     std::vector<int32_t> v(3 * nc);
-    HIP_OK(hipMemcpy(v.data(), dv.p, 3 * nc * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(v.data(), d_v, 3 * nc * 4, hipMemcpyDeviceToHost));
     int zeros = 0, ones = 0;
     for (size_t c = 0; c < nc; c++) {
         int kind = (int)(c % 8);
@@ -1097,15 +1086,138 @@ static int aggrlc_init_tables(void) {
     return HBLS_OK;
 }
 
-/* does this call take the combined path?  Mode 1 asks for it from the
- * threshold up; auto additionally stays off the latency (coop) sizes and
- * off the experiment switches, which select an exact kernel by name. */
+/* does a call over `batch` items take the combined path?  Mode 1 asks for it
+ * from the threshold up; auto additionally stays off the latency (coop) sizes
+ * and off the experiment switches, which select an exact kernel by name. */
 static bool aggrlc_wanted(size_t batch) {
-    int m = agg_verify_mode();
+    int m = aggrlc_switch(AGGRLC_SW_MODE, batch);
     if (m == 0 || !g_aggrlc_gtab) return false;
     if (batch > RLC_MAX_ITEMS || (long long)batch < (long long)g_aggrlc_threshold) return false;
     if (m == 1) return true;
     return (int)batch > coop_threshold() && rf_mode() == 0 && !use_batch_affine();
+}
+
+/* the one place a call reads the switches.  Combined or exact is decided on
+ * mode_batch (the size the caller was given), the leg and the hoisting on the
+ * items that reach the pairing stage; may_hoist: the caller runs the early part */
+static AggrlcPlan aggrlc_plan(size_t batch, size_t mode_batch, bool may_hoist) {
+    AggrlcPlan p = { false, 0, false, 0, 0, 0 };
+    p.combined = aggrlc_wanted(mode_batch);
+    if (!p.combined) return p;
+    p.leg = aggrlc_switch(AGGRLC_SW_SIGLEG, batch);
+    p.hoisted = may_hoist && p.leg && aggrlc_switch(AGGRLC_SW_EARLY, batch);
+    if (p.leg) p.level = aggrlc_switch(AGGRLC_SW_MILLER, batch);
+    p.final_kernel = aggrlc_switch(AGGRLC_SW_FINAL, batch);
+    if (p.hoisted) p.chunkleg_kernel = aggrlc_switch(AGGRLC_SW_CHUNKLEG, batch);
+    return p;
+}
+
+/* one combined call, as its stages below see it */
+struct AggrlcRun {
+    const AggrlcPlan &plan;
+    const g1_t *d_agg; const g2_t *d_hm; const g2aff_t *d_saff;
+    const int32_t *d_sflags, *d_hok;
+    int32_t *d_res;
+    size_t batch, nc;
+    const AggrlcBufs &L;
+};
+
+/* the Miller legs of the items — and, with the chunk-level leg not hoisted,
+ * of the chunk entries behind them: one dispatch on the plan */
+static void launch_aggrlc_items(const AggrlcRun &r) {
+    const AggrlcBufs &L = r.L;
+    if (!r.plan.leg) {
+        hipLaunchKernelGGL(k_aggrlc_miller, dim3((uint32_t)((r.batch + 63) / 64)), dim3(64), 0, 0,
+                           r.d_agg, r.d_hm, r.d_saff, r.d_sflags, r.d_hok,
+                           (const uint64_t *)L.sc, g_aggrlc_gtab, r.L.F, L.elig, r.d_res,
+                           (int)r.batch);
+        return;
+    }
+    static const decltype(&k_aggrlc_item<false, 0>) kernels[2][3] = {
+        { k_aggrlc_item<false, 0>, k_aggrlc_item<false, 1>, k_aggrlc_item<false, 2> },
+        { k_aggrlc_item<true, 0>, k_aggrlc_item<true, 1>, k_aggrlc_item<true, 2> } };
+    /* level 2: a block per chunk, then the entries, thread per chunk; below
+     * it a thread per item and per entry */
+    const size_t nx = r.plan.hoisted ? 0 : r.nc;
+    const size_t blocks = r.plan.level == 2 ? r.nc + (nx + 63) / 64 : (r.batch + nx + 63) / 64;
+    hipLaunchKernelGGL(kernels[r.plan.hoisted ? 1 : 0][r.plan.level], dim3((uint32_t)blocks),
+                       dim3(64), 0, 0, r.d_agg, r.d_hm, (const uint64_t *)L.sc,
+                       (const g2aff_t *)L.S, (const int32_t *)L.sflag, r.L.F, L.FX, L.elig,
+                       r.d_res, (int)r.batch, (int)r.nc, L.dirty, r.L.FC, r.L.ccnt, r.L.cforce);
+}
+
+/* hoisted: the join with the side stream's chunk entries, then the repair,
+ * over all chunks: blocks and threads of clean chunks return at once */
+static void launch_aggrlc_join_repair(const AggrlcRun &r, hipEvent_t legs_done) {
+    const AggrlcBufs &L = r.L;
+    (void)hipStreamWaitEvent(0, legs_done, 0);
+    hipLaunchKernelGGL(k_aggrlc_sigsum<true>, dim3((uint32_t)r.nc), dim3(AGGRLC_CHUNK), 0, 0,
+                       L.B, (int)r.batch, (int)r.nc, L.S, L.sflag, L.elig, L.dirty);
+    hipLaunchKernelGGL(k_aggrlc_chunkleg, dim3((uint32_t)((r.nc + 63) / 64)), dim3(64), 0, 0,
+                       L.S, L.sflag, L.dirty, L.FX, (int)r.nc);
+}
+
+/* FC[c]: the chunk's product with its own entry — a tree over F, or at
+ * level 2 the entry folded into what the item kernel left */
+static void launch_aggrlc_products(const AggrlcRun &r) {
+    if (r.plan.level == 2)
+        hipLaunchKernelGGL(k_aggrlc_chunk_fold, dim3((uint32_t)((r.nc + 63) / 64)), dim3(64), 0, 0,
+                           r.L.FC, r.L.FX, (int)r.nc);
+    else
+        hipLaunchKernelGGL(k_aggrlc_chunk_prod, dim3((uint32_t)r.nc), dim3(AGGRLC_CHUNK), 0, 0,
+                           r.L.F, r.L.elig, (int)r.batch, (int)r.nc, r.L.FC, r.L.ccnt,
+                           r.L.cforce, r.plan.leg ? r.L.FX : (const fp12_t *)nullptr);
+}
+
+/* ccnt | cforce | verdict to the host (the call's first wait for the device)
+ * and the stage slots: ev[0..4] bound 7, 4, 5, 6; hoisted, 7 and 8 come from
+ * the early part's own events */
+static int aggrlc_download(const AggrlcRun &r, const EventSet<5> &ev, const AggrlcEarly *early,
+                           std::vector<int32_t> &hc) {
+    hipError_t e = hipMemcpy(hc.data(), r.L.ccnt, 3 * r.nc * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipGetLastError();
+    auto ns = [e](hipEvent_t a, hipEvent_t b) {         /* zero after an error */
+        float ms = 0;
+        if (e == hipSuccess) (void)hipEventElapsedTime(&ms, a, b);
+        return (uint64_t)(ms * 1e6);
+    };
+    for (int i = 1; i < 4; i++) g_stage_ns[3 + i] = ns(ev[i], ev[i + 1]);
+    g_stage_ns[7] = early ? ns(early->ev[0], early->ev[1]) : r.plan.leg ? ns(ev[0], ev[1]) : 0;
+    if (early && e == hipSuccess) g_stage_ns[8] = ns(early->ev[2], early->ev[3]);
+    HIP_OK(e);
+    return HBLS_OK;
+}
+
+/* the statistics, and the refinement, one level: the eligible items of
+ * failing chunks go through the exact per-item pairing */
+static int aggrlc_refine(const AggrlcRun &r, const std::vector<int32_t> &hc) {
+    std::vector<uint32_t> failed;
+    for (size_t c = 0; c < r.nc; c++) {
+        if (hc[c] <= 0) continue;
+        g_aggrlc_stats[0]++;
+        if (hc[2 * r.nc + c] == 1) continue;
+        g_aggrlc_stats[1]++;
+        failed.push_back((uint32_t)c);
+    }
+    if (failed.empty()) return HBLS_OK;
+    std::vector<int32_t> helig(r.batch);
+    HIP_OK(hipMemcpy(helig.data(), r.L.elig, r.batch * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> sel;
+    for (uint32_t c : failed)
+        for (size_t i = (size_t)c * AGGRLC_CHUNK;
+             i < r.batch && i < ((size_t)c + 1) * AGGRLC_CHUNK; i++)
+            if (helig[i]) sel.push_back((uint32_t)i);
+    size_t ns = sel.size();
+    g_aggrlc_stats[2] = (uint32_t)ns;
+    if (!ns) return HBLS_OK;
+    DevBuf dsel(ns * 4);
+    if (dsel.err) return HBLS_ERR;
+    HIP_OK(hipMemcpy(dsel.p, sel.data(), ns * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_verify_sel, dim3((uint32_t)((ns + 63) / 64)), dim3(64), 0, 0,
+                       dsel.as<uint32_t>(), (int)ns, r.d_agg, r.d_hm, r.d_saff, r.d_sflags,
+                       r.d_hok, r.d_res, (int)r.batch);
+    HIP_OK(hipGetLastError());
+    return HBLS_OK;
 }
 
 /* the verify stage of run_agg_verify_pipeline on the combined path; inputs
@@ -1116,175 +1228,53 @@ static bool aggrlc_wanted(size_t batch) {
  * leg (zero with the per-item leg).  Every launch lies between the caller's
  * verify-stage events.
  * With `early` (the hoisted schedule) the scalars, the signature chain and
- * the chunk legs are the pipeline's earlier work: what remains is the Miller
- * kernel over the items, the join with the side stream, the repair of dirty
- * chunks, products and final.  g_stage_ns[4] then covers the Miller kernel,
- * the join and the repair launches, g_stage_ns[7] the early part's own
- * interval and g_stage_ns[8] the chunk-leg kernel's on its stream. */
-static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_saff,
-                         const int32_t *d_sflags, const int32_t *d_hok,
+ * the chunk legs are the pipeline's earlier work.  g_stage_ns[4] then covers
+ * the item kernel, the join and the repair launches, g_stage_ns[7] the early
+ * part's own interval and g_stage_ns[8] the chunk-leg kernel's on its stream. */
+static int aggrlc_verify(const AggrlcPlan &plan, const g1_t *d_agg, const g2_t *d_hm,
+                         const g2aff_t *d_saff, const int32_t *d_sflags, const int32_t *d_hok,
                          int32_t *d_res, size_t batch, AggrlcEarly *early) {
-    size_t nc = (batch + AGGRLC_CHUNK - 1) / AGGRLC_CHUNK;
-    const int leg = early ? 1 : aggrlc_sigleg(batch);
-    const size_t nx = (leg && !early) ? nc : 0;     /* chunk entries behind the items' f */
-    const int lvl = leg ? aggrlc_miller_level() : 0;
-    const bool fused = lvl == 2;                    /* no F: the Miller kernel stores FC */
+    const size_t nc = (batch + AGGRLC_CHUNK - 1) / AGGRLC_CHUNK;
     std::vector<uint64_t> scalars(early ? 0 : batch);
     if (!early && !rlc_draw_scalars(scalars.data(), batch)) return AGGRLC_FALLBACK;
     FreeClock fclk;
     uint64_t t_alloc = host_now_ns();
-    /* dF: the items' f, then the chunk entries, then (chunk-level leg) the
-     * scaled signatures B and the chunk sums S — one allocation, so the
-     * per-item leg allocates what it always did; dcs: ccnt | cforce |
-     * verdict | sflag.  The hoisted schedule brings its own scalars, elig,
-     * B, S, sflag and chunk entries. */
-    const size_t nf = fused ? 0 : batch;
-    const size_t f_bytes = (nf + nx) * sizeof(fp12_t);
-    const size_t b_bytes = nx ? batch * sizeof(g2_t) : 0;
-    DevBuf dsc(early ? 0 : batch * 8), dF(f_bytes + b_bytes + nx * sizeof(g2aff_t));
-    DevBuf delig(early ? 0 : batch * 4);
-    DevBuf dFC(nc * sizeof(fp12_t)), dcs((3 * nc + nx) * 4);
+    std::unique_ptr<AggrlcBufs> own;    /* the hoisted schedule brings its own */
+    if (!early) own.reset(new (std::nothrow) AggrlcBufs(batch, nc, plan));
     g_host_ns[0] += host_now_ns() - t_alloc;
     FreeClockArm farm(fclk);
-    if (dsc.err || dF.err || delig.err || dFC.err || dcs.err) {
+    const AggrlcBufs *bufs = early ? &early->bufs : own.get();
+    if (!bufs || bufs->buf.err) {
         (void)hipGetLastError();
         return AGGRLC_FALLBACK;
     }
-    fp12_t *d_F = dF.as<fp12_t>();
-    g2_t *d_B = (g2_t *)((uint8_t *)dF.p + f_bytes);
-    g2aff_t *d_S = (g2aff_t *)((uint8_t *)dF.p + f_bytes + b_bytes);
-    const uint64_t *d_sc = early ? early->dsc.as<uint64_t>() : dsc.as<uint64_t>();
-    int32_t *d_elig = early ? early->delig.as<int32_t>() : delig.as<int32_t>();
+    const AggrlcRun r = { plan, d_agg, d_hm, d_saff, d_sflags, d_hok, d_res, batch, nc, *bufs };
     /* the scalars go up beside the kernels already queued, not behind them;
      * `scalars` outlives the copy (the verdict download below waits for the
      * Miller kernel, which waits for the upload) */
     EventSet<1> up;
     if (up.err != hipSuccess) return HBLS_ERR;
-    if (!early) HIP_OK(upload_then_wait(dsc.p, scalars.data(), batch * 8, up[0]));
-    int32_t *d_ccnt = dcs.as<int32_t>(), *d_cforce = d_ccnt + nc, *d_verdict = d_cforce + nc;
-    int32_t *d_sf = d_verdict + nc;
-    /* ev[0..1] around the signature scaling and sums, ev[1..4] as before */
+    if (!early) HIP_OK(upload_then_wait(bufs->sc, scalars.data(), batch * 8, up[0]));
+    /* ev[0..1] around the signature scaling and sums, then Miller (with the
+     * join and repair), products, final */
     EventSet<5> ev;
     if (ev.err != hipSuccess) return HBLS_ERR;
     (void)hipEventRecord(ev[0], 0);
-    if (leg && !early) {
-        hipLaunchKernelGGL(k_aggrlc_sigscale<false>, dim3((uint32_t)((batch + 63) / 64)), dim3(64),
-                           0, 0, d_agg, d_saff, d_sflags, d_hok, d_sc, d_B,
-                           d_elig, d_res, (int)batch);
-        hipLaunchKernelGGL(k_aggrlc_sigsum<false>, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
-                           d_B, (int)batch, (int)nc, d_S, d_sf,
-                           (const int32_t *)nullptr, (const int32_t *)nullptr);
-    }
+    if (plan.leg && !early)
+        launch_aggrlc_sig_chain(false, d_agg, d_saff, d_sflags, d_hok, *bufs, d_res, batch, nc);
     (void)hipEventRecord(ev[1], 0);
-    if (early) {
-        if (fused)
-            hipLaunchKernelGGL((k_aggrlc_miller1j<true, true>), dim3((uint32_t)nc), dim3(64),
-                               0, 0, d_agg, d_hm, d_sc, early->dS.as<g2aff_t>(), early->sflag(),
-                               d_F, d_elig, d_res, (int)batch, (int)nc, early->dirty(),
-                               dFC.as<fp12_t>(), d_ccnt, d_cforce);
-        else if (lvl == 1)
-            hipLaunchKernelGGL((k_aggrlc_miller1j<true, false>),
-                               dim3((uint32_t)((batch + 63) / 64)), dim3(64),
-                               0, 0, d_agg, d_hm, d_sc, early->dS.as<g2aff_t>(), early->sflag(),
-                               d_F, d_elig, d_res, (int)batch, 0, early->dirty(),
-                               (fp12_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
-        else
-            hipLaunchKernelGGL(k_aggrlc_miller1<true>, dim3((uint32_t)((batch + 63) / 64)),
-                               dim3(64), 0, 0, d_agg, d_hm, d_sc, early->dS.as<g2aff_t>(),
-                               early->sflag(), d_F, d_elig, d_res, (int)batch, 0, early->dirty());
-        /* join: the chunk entries are complete; then the repair, over all
-         * chunks — blocks and threads of clean chunks return at once */
-        (void)hipStreamWaitEvent(0, early->ev[3], 0);
-        hipLaunchKernelGGL(k_aggrlc_sigsum<true>, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
-                           early->dB.as<g2_t>(), (int)batch, (int)nc, early->dS.as<g2aff_t>(),
-                           early->sflag(), d_elig, early->dirty());
-        hipLaunchKernelGGL(k_aggrlc_chunkleg, dim3((uint32_t)((nc + 63) / 64)), dim3(64), 0, 0,
-                           early->dS.as<g2aff_t>(), early->sflag(), early->dirty(),
-                           early->dFX.as<fp12_t>(), (int)nc);
-    } else if (fused) {
-        /* nc item blocks, then the chunk entries, thread per chunk, into d_F */
-        hipLaunchKernelGGL((k_aggrlc_miller1j<false, true>),
-                           dim3((uint32_t)(nc + (nc + 63) / 64)), dim3(64), 0, 0, d_agg, d_hm,
-                           d_sc, d_S, d_sf, d_F, d_elig, d_res, (int)batch, (int)nc,
-                           (int32_t *)nullptr, dFC.as<fp12_t>(), d_ccnt, d_cforce);
-    } else if (lvl == 1) {
-        hipLaunchKernelGGL((k_aggrlc_miller1j<false, false>),
-                           dim3((uint32_t)((batch + nc + 63) / 64)), dim3(64), 0, 0, d_agg, d_hm,
-                           d_sc, d_S, d_sf, d_F, d_elig, d_res, (int)batch, (int)nc,
-                           (int32_t *)nullptr, (fp12_t *)nullptr, (int32_t *)nullptr,
-                           (int32_t *)nullptr);
-    } else if (leg) {
-        hipLaunchKernelGGL(k_aggrlc_miller1<false>, dim3((uint32_t)((batch + nc + 63) / 64)),
-                           dim3(64), 0, 0, d_agg, d_hm, d_sc, d_S, d_sf, d_F,
-                           d_elig, d_res, (int)batch, (int)nc, (int32_t *)nullptr);
-    } else {
-        hipLaunchKernelGGL(k_aggrlc_miller, dim3((uint32_t)((batch + 63) / 64)), dim3(64), 0, 0,
-                           d_agg, d_hm, d_saff, d_sflags, d_hok, d_sc,
-                           g_aggrlc_gtab, d_F, d_elig, d_res, (int)batch);
-    }
+    launch_aggrlc_items(r);
+    if (early) launch_aggrlc_join_repair(r, early->ev[3]);
     (void)hipEventRecord(ev[2], 0);
-    const fp12_t *d_FX = early ? early->dFX.as<fp12_t>()
-                               : leg ? d_F + nf : (const fp12_t *)nullptr;
-    if (fused)
-        hipLaunchKernelGGL(k_aggrlc_chunk_fold, dim3((uint32_t)((nc + 63) / 64)), dim3(64), 0, 0,
-                           dFC.as<fp12_t>(), d_FX, (int)nc);
-    else
-        hipLaunchKernelGGL(k_aggrlc_chunk_prod, dim3((uint32_t)nc), dim3(AGGRLC_CHUNK), 0, 0,
-                           d_F, d_elig, (int)batch, (int)nc,
-                           dFC.as<fp12_t>(), d_ccnt, d_cforce, d_FX);
+    launch_aggrlc_products(r);
     (void)hipEventRecord(ev[3], 0);
-    launch_aggrlc_final(aggrlc_final_kernel(), dFC.as<fp12_t>(), d_ccnt, d_cforce,
-                        d_verdict, (int)nc);
+    launch_aggrlc_final(plan.final_kernel, bufs->FC, bufs->ccnt, bufs->cforce, bufs->verdict,
+                        (int)nc);
     (void)hipEventRecord(ev[4], 0);
     std::vector<int32_t> hc(3 * nc);
-    hipError_t e = hipMemcpy(hc.data(), dcs.p, 3 * nc * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipGetLastError();
-    for (int i = 0; i < 4; i++) {
-        float ms = 0;
-        if (e == hipSuccess && (i || (leg && !early)))
-            (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-        g_stage_ns[i ? 3 + i : 7] = (uint64_t)(ms * 1e6);
-    }
-    if (early && e == hipSuccess) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, early->ev[0], early->ev[1]);
-        g_stage_ns[7] = (uint64_t)(ms * 1e6);
-        ms = 0;
-        (void)hipEventElapsedTime(&ms, early->ev[2], early->ev[3]);
-        g_stage_ns[8] = (uint64_t)(ms * 1e6);
-    }
-    HIP_OK(e);
-
-    std::vector<uint32_t> failed;
-    for (size_t c = 0; c < nc; c++) {
-        if (hc[c] <= 0) continue;
-        g_aggrlc_stats[0]++;
-        if (hc[2 * nc + c] == 1) continue;
-        g_aggrlc_stats[1]++;
-        failed.push_back((uint32_t)c);
-    }
-    if (failed.empty()) return HBLS_OK;
-
-    /* refinement, one level: the eligible items of failing chunks go through
-     * the exact per-item pairing */
-    std::vector<int32_t> helig(batch);
-    HIP_OK(hipMemcpy(helig.data(), d_elig, batch * 4, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> sel;
-    for (uint32_t c : failed)
-        for (size_t i = (size_t)c * AGGRLC_CHUNK;
-             i < batch && i < ((size_t)c + 1) * AGGRLC_CHUNK; i++)
-            if (helig[i]) sel.push_back((uint32_t)i);
-    size_t ns = sel.size();
-    g_aggrlc_stats[2] = (uint32_t)ns;
-    if (!ns) return HBLS_OK;
-    DevBuf dsel(ns * 4);
-    if (dsel.err) return HBLS_ERR;
-    HIP_OK(hipMemcpy(dsel.p, sel.data(), ns * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_verify_sel, dim3((uint32_t)((ns + 63) / 64)), dim3(64), 0, 0,
-                       dsel.as<uint32_t>(), (int)ns, d_agg, d_hm, d_saff, d_sflags, d_hok,
-                       d_res, (int)batch);
-    HIP_OK(hipGetLastError());
-    return HBLS_OK;
+    int rc = aggrlc_download(r, ev, early, hc);
+    if (rc != HBLS_OK) return rc;
+    return aggrlc_refine(r, hc);
 }
 
 /* ---- test hook for the functions above (not part of the ABI, kept out of

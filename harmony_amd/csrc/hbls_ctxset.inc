@@ -511,7 +511,8 @@ extern "C" int hbls_batch_seal_verify_ctx(const hbls_ctxset_t *s, const uint32_t
     std::vector<int32_t> sub(nlive);
     rc = run_agg_verify_pairing(dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
                                 dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(),
-                                nlive, batch, ev, t_launch, sub.data());
+                                nlive, aggrlc_plan(nlive, batch, false), ev, t_launch,
+                                sub.data());
     if (rc != HBLS_OK) return rc;
     g_last_ns += front_ns;
     g_stage_ns[7] = front_ns;

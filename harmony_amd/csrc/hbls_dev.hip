@@ -2389,6 +2389,7 @@ __global__ void k_keccak(const uint8_t *msgs, int mlen, uint8_t *outs, int batch
 #include "hbls_coop.inc"
 
 /* ================================================================ host layer */
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -2409,7 +2410,6 @@ static std::once_flag g_init_flag;
 static int g_init_rc = HBLS_ERR_NOGPU;
 /* combined aggregate verify (hbls_aggrlc.inc, included below) */
 static int aggrlc_init_tables(void);
-static bool aggrlc_wanted(size_t batch);
 static void aggrlc_stats_reset(void);
 
 #define HIP_OK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
@@ -2864,15 +2864,22 @@ extern "C" int hbls_mask_aggregate_g1(const hbls_committee_t *c, const uint8_t *
  * §4l): the state its early part hands to aggrlc_verify, null when nothing
  * was hoisted */
 struct AggrlcEarly;
-static AggrlcEarly *aggrlc_early_begin(const g2aff_t *d_saff, const int32_t *d_sflags,
-                                       const int32_t *d_hok, int32_t *d_res, size_t batch);
+/* what one call does on the combined path, resolved from the switches once
+ * (aggrlc_plan) and read by everything after: combined or exact, where the
+ * signature leg is paired (0 per item, 1 per chunk), whether the chunk-level
+ * leg is hoisted, the item kernel's level, the final and chunk-leg kernels */
+struct AggrlcPlan { bool combined; int leg; bool hoisted; int level, final_kernel, chunkleg_kernel; };
+static AggrlcPlan aggrlc_plan(size_t batch, size_t mode_batch, bool may_hoist);
+static AggrlcEarly *aggrlc_early_begin(AggrlcPlan &plan, const g2aff_t *d_saff,
+                                       const int32_t *d_sflags, const int32_t *d_hok,
+                                       int32_t *d_res, size_t batch);
 static void aggrlc_early_free(AggrlcEarly *e);
 struct AggrlcEarlyHold {
     AggrlcEarly *p = nullptr;
     ~AggrlcEarlyHold() { if (p) aggrlc_early_free(p); }
 };
-static int aggrlc_verify(const g1_t *d_agg, const g2_t *d_hm, const g2aff_t *d_saff,
-                         const int32_t *d_sflags, const int32_t *d_hok,
+static int aggrlc_verify(const AggrlcPlan &plan, const g1_t *d_agg, const g2_t *d_hm,
+                         const g2aff_t *d_saff, const int32_t *d_sflags, const int32_t *d_hok,
                          int32_t *d_res, size_t batch, AggrlcEarly *early);
 #define AGGRLC_FALLBACK 2       /* aggrlc_verify wrote nothing: run the exact path */
 
@@ -2884,22 +2891,22 @@ struct AggHostSrc { const uint8_t *bitmaps, *sigs, *msgs; };
  * exact or the combined check over masked key sums, hash points and
  * decompressed signatures already enqueued on the null stream, then the
  * stage intervals (ev[2s], ev[2s+1] around stage s; ev[2] is the call's
- * first event) and the verdicts to the host.  mode_batch is the batch size
- * the exact/combined rule is applied to.  Shared by run_agg_verify_pipeline
+ * first event) and the verdicts to the host.  plan is the caller's, resolved
+ * once for the call (aggrlc_plan).  Shared by run_agg_verify_pipeline
  * and the epoch-context entry (hbls_ctxset.inc).  With `early` the pipeline
  * has hoisted the combined path's signature chain, so the combined path it
  * is; that chain's interval lies ahead of the verify events and is added to
  * stage 3, so the four stages still add up to the call's kernel time. */
 static int run_agg_verify_pairing(const g1_t *d_agg, g2_t *d_hm, g2aff_t *d_saff,
                                   int32_t *d_sflags, int32_t *d_hok, int32_t *d_res,
-                                  size_t batch, size_t mode_batch, const EventSet<8> &ev,
+                                  size_t batch, const AggrlcPlan &plan, const EventSet<8> &ev,
                                   uint64_t t_launch, int32_t *results,
                                   AggrlcEarly *early = nullptr) {
     int nb = (int)((batch + 63) / 64);
     (void)hipEventRecord(ev[6], 0);
     int arc = AGGRLC_FALLBACK;
-    if (early || aggrlc_wanted(mode_batch)) {
-        arc = aggrlc_verify(d_agg, d_hm, d_saff, d_sflags, d_hok, d_res, batch, early);
+    if (plan.combined) {
+        arc = aggrlc_verify(plan, d_agg, d_hm, d_saff, d_sflags, d_hok, d_res, batch, early);
         if (arc != HBLS_OK && arc != AGGRLC_FALLBACK) return arc;
     }
     if (arc == HBLS_OK) {
@@ -3001,9 +3008,10 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
     /* the combined path's signature chain and chunk legs, ahead of and
      * beside the mask kernel (declared after the buffers and events above:
      * it waits for its side stream before they go) */
+    AggrlcPlan plan = aggrlc_plan(batch, batch, true);
     AggrlcEarlyHold early;
-    early.p = aggrlc_early_begin(dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), dhok.as<int32_t>(),
-                                 dres.as<int32_t>(), batch);
+    early.p = aggrlc_early_begin(plan, dsaff.as<g2aff_t>(), dsflags.as<int32_t>(),
+                                 dhok.as<int32_t>(), dres.as<int32_t>(), batch);
 
     if (src) HIP_OK(upload_then_wait((void *)d_bm, src->bitmaps, batch * bm, up[2]));
     (void)hipEventRecord(ev[0], 0);
@@ -3014,7 +3022,7 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
 
     return run_agg_verify_pairing(dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
                                   dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(),
-                                  batch, batch, ev, t_launch, results, early.p);
+                                  batch, plan, ev, t_launch, results, early.p);
 }
 
 extern "C" int hbls_batch_agg_verify(const hbls_committee_t *c, const uint8_t *bitmaps,

@@ -10,7 +10,6 @@ three combined runs must report equal core.aggrlc_last_stats().  The hoisted
 run uses the default chunk-leg kernel (four lanes per chunk); the all-valid
 and wrong-signature cases repeat it with the one-lane kernel."""
 import os
-import random
 import sys
 
 import pytest
@@ -18,96 +17,31 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-pytestmark = pytest.mark.gpu
+from aggrlc_env import BAD, Env, _chunks, gpu_marks, init_core  # noqa: E402
 
-from oracle import pyref as pr  # noqa: E402
-
-
-def _gpu_available():
-    try:
-        from harmony_amd import core
-        return core.device_count() > 0
-    except Exception:
-        return False
-
-
-if not os.environ.get("HBLS_FORCE_GPU_TESTS"):
-    pytestmark = [pytest.mark.gpu,
-                  pytest.mark.skipif(not _gpu_available(), reason="no AMD GPU")]
+pytestmark = gpu_marks()
 
 
 @pytest.fixture(scope="module")
 def core():
-    from harmony_amd import core as c
-    c.init(-1 if c.device_count() == 0 else 0)
-    return c
+    return init_core()
 
 
-N = 64                      # committee
 BATCHES = [1, 63, 64, 65, 129, 130]
 TOTAL = max(BATCHES)
-BAD = -1                    # any negative code (the oracle and the library number them apart)
 
 
-def _norm(res):
-    return [BAD if v < 0 else v for v in res]
-
-
-class _Env:
-    """64 keys and 130 valid (mask, message, aggregate signature) items plus
-    the forged signature the tests swap in — built once, never modified"""
-
-    def __init__(self, capi, core):
-        self.core = core
-        self.capi = capi
-        rng = random.Random(7)
-        sk = [pr.synth_sk(300 + i) for i in range(N)]
-        self.pks = core.batch_pk_from_sk(b"".join(pr.fr_serialize(k) for k in sk), N)
-        self.committee = core.Committee(self.pks, N)
-        self.oracle = capi.Committee(self.pks, N)
-        self.bmlen = (N + 7) // 8
-        self.masks, self.msgs, agg_sk = [], [], []
-        for j in range(TOTAL):
-            signers = rng.sample(range(N), rng.randrange(1, N + 1))
-            bm = bytearray(self.bmlen)
-            for i in signers:
-                bm[i >> 3] |= 1 << (i & 7)
-            self.masks.append(bytes(bm))
-            self.msgs.append(pr.construct_commit_payload(j, pr.synth_msg(500 + j), j + 1))
-            agg_sk.append(sum(sk[i] for i in signers) % pr.R)
-        self.mlen = len(self.msgs[0])
-        cat = core.batch_sign(b"".join(pr.fr_serialize(k) for k in agg_sk),
-                              b"".join(self.msgs), self.mlen, TOTAL)
-        self.sigs = [cat[96 * j:96 * (j + 1)] for j in range(TOTAL)]
-        self.D = capi.sign_hash(pr.fr_serialize(pr.synth_sk(999)), self.msgs[0])
-        assert core.aggrlc_chunk_size() == 64
-
+class _Env(Env):
     def configured(self, mode, leg, early, call, kernel=-1):
         """(results, stats, stage slots 7 and 8) of one call under the setting"""
-        core = self.core
-        core.set_agg_verify_mode(mode)
-        core.set_aggrlc_threshold(1)
-        core.set_aggrlc_sigleg(leg)
-        core.set_aggrlc_early(early)
-        core.set_aggrlc_chunkleg(kernel)
-        try:
-            res = call()
-            stats = core.aggrlc_last_stats()
-            slots = (core.last_stage_ns(7), core.last_stage_ns(8))
-        finally:
-            core.set_agg_verify_mode(-1)
-            core.set_aggrlc_threshold(-1)
-            core.set_aggrlc_sigleg(-1)
-            core.set_aggrlc_early(-1)
-            core.set_aggrlc_chunkleg(-1)
-        return _norm(res), stats, slots
+        res, stats, slots = super().configured(call, mode=mode, sigleg=leg, early=early,
+                                               chunkleg=kernel)
+        return res, stats, (slots[7], slots[8])
 
     def run(self, mode, leg, early, batch, sigs=None, masks=None, kernel=-1):
-        sigs = self.sigs if sigs is None else sigs
-        masks = self.masks if masks is None else masks
-        return self.configured(mode, leg, early, lambda: self.committee.batch_agg_verify(
-            b"".join(masks[:batch]), b"".join(sigs[:batch]),
-            b"".join(self.msgs[:batch]), self.mlen, batch), kernel)
+        a = self.args(batch, sigs, masks)
+        return self.configured(mode, leg, early,
+                               lambda: self.committee.batch_agg_verify(*a), kernel)
 
     def check(self, batch, expect, sigs=None, masks=None, onelane=False):
         """early 1 == early 0 == leg 0 == mode 0 == oracle == expect, the three
@@ -126,11 +60,7 @@ class _Env:
         assert r0 == expect
         assert rl == expect
         assert rx == expect
-        sigs = self.sigs if sigs is None else sigs
-        masks = self.masks if masks is None else masks
-        assert _norm(self.oracle.batch_agg_verify(
-            b"".join(masks[:batch]), b"".join(sigs[:batch]),
-            b"".join(self.msgs[:batch]), self.mlen, batch)) == expect
+        assert self.oracle_run(batch, sigs, masks) == expect
         assert s1 == s0 == sl
         assert t1[0] > 0 and t1[1] > 0          # hoisted: sigscale + sigsum, chunk legs
         assert t0[0] > 0 and t0[1] == 0
@@ -140,11 +70,7 @@ class _Env:
 
 @pytest.fixture(scope="module")
 def env(oracle_lib, core):
-    return _Env(oracle_lib, core)
-
-
-def _chunks(batch):
-    return (batch + 63) // 64
+    return _Env(oracle_lib, core, seed=7)
 
 
 @pytest.mark.parametrize("batch", BATCHES)
@@ -221,25 +147,18 @@ def test_undecodable_signature(env):
     assert env.check(65, expect, sigs=sigs) == [2, 0, 0]
 
 
-def _cancelling(env, a, b):
-    sigs = list(env.sigs)
-    sigs[a] = env.capi.g2_add(env.sigs[a], env.D)
-    sigs[b] = env.capi.g2_add(env.sigs[b], env.D, sub=True)
-    return sigs
-
-
 def test_cancelling_pair_in_one_chunk(env):
     a, b = 3, 41
     expect = [1] * 65
     expect[a] = expect[b] = 0
-    assert env.check(65, expect, sigs=_cancelling(env, a, b)) == [2, 1, 64]
+    assert env.check(65, expect, sigs=env.cancelling(a, b)) == [2, 1, 64]
 
 
 def test_cancelling_pair_across_chunks(env):
     a, b = 10, 70
     expect = [1] * TOTAL
     expect[a] = expect[b] = 0
-    assert env.check(TOTAL, expect, sigs=_cancelling(env, a, b)) == [3, 2, 128]
+    assert env.check(TOTAL, expect, sigs=env.cancelling(a, b)) == [3, 2, 128]
 
 
 # ------------------------------------------------------------------ other entries
@@ -276,11 +195,7 @@ def test_ctxset_seal_verify_keeps_its_sequence(env):
 @pytest.mark.parametrize("early", [2, -2])
 def test_setter_rejects(env, early):
     core = env.core
-    core.set_agg_verify_mode(1)
-    core.set_aggrlc_threshold(1)
-    core.set_aggrlc_sigleg(1)
-    core.set_aggrlc_early(1)
-    try:
+    with core.aggrlc_switches(mode=1, threshold=1, sigleg=1, early=1):
         with pytest.raises(ValueError):
             core.set_aggrlc_early(early)
         # the rejected call changed nothing: the next call is still hoisted
@@ -297,8 +212,3 @@ def test_setter_rejects(env, early):
         assert res == [1, 1, 1]
         assert core.last_stage_ns(7) > 0
         assert core.last_stage_ns(8) == 0
-    finally:
-        core.set_agg_verify_mode(-1)
-        core.set_aggrlc_threshold(-1)
-        core.set_aggrlc_sigleg(-1)
-        core.set_aggrlc_early(-1)

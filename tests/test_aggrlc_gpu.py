@@ -3,96 +3,26 @@ verdicts of Committee.batch_agg_verify must equal the exact per-item path's
 (mode 0) and the CPU oracle's, with the shared final exponentiations and the
 refinement shown by core.aggrlc_last_stats()."""
 import os
-import random
 import sys
 
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-pytestmark = pytest.mark.gpu
+from aggrlc_env import BAD, Env, _chunks, gpu_marks  # noqa: E402
 
-from oracle import pyref as pr  # noqa: E402
+pytestmark = gpu_marks()
 
-
-def _gpu_available():
-    try:
-        from harmony_amd import core
-        return core.device_count() > 0
-    except Exception:
-        return False
-
-
-if not os.environ.get("HBLS_FORCE_GPU_TESTS"):
-    pytestmark = [pytest.mark.gpu,
-                  pytest.mark.skipif(not _gpu_available(), reason="no AMD GPU")]
-
-N = 64                      # committee
 BATCHES = [1, 63, 64, 65, 130]
 TOTAL = max(BATCHES)
-BAD = -1                    # any negative code (the oracle and the library number them apart)
 
 
-def _norm(res):
-    return [BAD if v < 0 else v for v in res]
-
-
-class _Env:
-    """64 keys and 130 valid (mask, message, aggregate signature) items plus
-    the forged signatures the tests swap in — built once, never modified.
-    An item's aggregate signature is one signature under the sum of its
-    signers' secret keys (BLS is linear in the key)."""
-
-    def __init__(self, capi):
-        from harmony_amd import core
-        self.core = core
-        self.capi = capi
-        rng = random.Random(4)
-        sk = [pr.synth_sk(300 + i) for i in range(N)]
-        self.pks = core.batch_pk_from_sk(b"".join(pr.fr_serialize(k) for k in sk), N)
-        self.committee = core.Committee(self.pks, N)
-        self.oracle = capi.Committee(self.pks, N)
-        self.bmlen = (N + 7) // 8
-        self.masks, self.msgs, agg_sk = [], [], []
-        for j in range(TOTAL):
-            signers = rng.sample(range(N), rng.randrange(1, N + 1))
-            bm = bytearray(self.bmlen)
-            for i in signers:
-                bm[i >> 3] |= 1 << (i & 7)
-            self.masks.append(bytes(bm))
-            self.msgs.append(pr.construct_commit_payload(j, pr.synth_msg(500 + j), j + 1))
-            agg_sk.append(sum(sk[i] for i in signers) % pr.R)
-        self.mlen = len(self.msgs[0])
-        cat = core.batch_sign(b"".join(pr.fr_serialize(k) for k in agg_sk),
-                              b"".join(self.msgs), self.mlen, TOTAL)
-        self.sigs = [cat[96 * j:96 * (j + 1)] for j in range(TOTAL)]
-        self.D = capi.sign_hash(pr.fr_serialize(pr.synth_sk(999)), self.msgs[0])
-        assert core.aggrlc_chunk_size() == 64
-
+class _Env(Env):
     def run(self, mode, batch, sigs=None, masks=None):
         """(normalised verdicts, stats) of one batch_agg_verify call over the
         first `batch` items in the given mode"""
-        core = self.core
-        sigs = self.sigs if sigs is None else sigs
-        masks = self.masks if masks is None else masks
-        core.set_agg_verify_mode(mode)
-        core.set_aggrlc_threshold(1)
-        try:
-            res = self.committee.batch_agg_verify(
-                b"".join(masks[:batch]), b"".join(sigs[:batch]),
-                b"".join(self.msgs[:batch]), self.mlen, batch)
-            stats = core.aggrlc_last_stats()
-        finally:
-            core.set_agg_verify_mode(-1)
-            core.set_aggrlc_threshold(-1)
-        return _norm(res), stats
-
-    def oracle_run(self, batch, sigs=None, masks=None):
-        sigs = self.sigs if sigs is None else sigs
-        masks = self.masks if masks is None else masks
-        return _norm(self.oracle.batch_agg_verify(
-            b"".join(masks[:batch]), b"".join(sigs[:batch]),
-            b"".join(self.msgs[:batch]), self.mlen, batch))
+        return super().run(batch, sigs, masks, mode=mode)[:2]
 
     def check(self, batch, expect, sigs=None, masks=None):
         """mode 1 == mode 0 == oracle == expect; returns mode 1's stats"""
@@ -107,11 +37,8 @@ class _Env:
 
 @pytest.fixture(scope="module")
 def env(oracle_lib):
-    return _Env(oracle_lib)
-
-
-def _chunks(batch):
-    return (batch + 63) // 64
+    from harmony_amd import core
+    return _Env(oracle_lib, core, seed=4)
 
 
 @pytest.mark.parametrize("batch", BATCHES)
@@ -135,9 +62,7 @@ def test_cancelling_pair_in_one_chunk(env):
     """sig_a + D and sig_b - D: the unweighted product of the two items
     passes, the weighted one must not"""
     a, b = 3, 41
-    sigs = list(env.sigs)
-    sigs[a] = env.capi.g2_add(env.sigs[a], env.D)
-    sigs[b] = env.capi.g2_add(env.sigs[b], env.D, sub=True)
+    sigs = env.cancelling(a, b)
     expect = [1] * 65
     expect[a] = expect[b] = 0
     stats = env.check(65, expect, sigs=sigs)
@@ -175,6 +100,33 @@ def test_empty_mask_identity_signature(env):
     assert stats == [1, 0, 0]
 
 
+def test_every_class_in_one_chunk(env):
+    """the one classification routine under every kernel that
+    calls it: chunk 0 holds a wrong signature, an undecodable one, the herumi
+    accept (empty mask, identity signature), an empty mask under a real
+    signature and an identity signature under a real mask; item 64 is valid
+    and alone in chunk 1.  Chunk 0 fails on the wrong signature, and four of
+    its items are classified without a pairing: 60 go to the per-item path."""
+    sigs, masks = list(env.sigs), list(env.masks)
+    sigs[3] = env.sigs[4]                   # a valid point, the wrong one
+    sigs[5] = b"\xff" * 96
+    sigs[7], masks[7] = b"\x00" * 96, bytes(env.bmlen)
+    masks[9] = bytes(env.bmlen)
+    sigs[11] = b"\x00" * 96
+    expect = [1] * 65
+    expect[3], expect[5], expect[9], expect[11] = 0, BAD, 0, 0
+    assert env.oracle_run(65, sigs, masks) == expect
+    assert env.run(0, 65, sigs, masks) == (expect, [0, 0, 0])
+    combined = [dict(sigleg=0)] + [dict(sigleg=1, early=early, miller=level)
+                                   for early in (0, 1) for level in (0, 1, 2)]
+    for switches in combined:
+        res, stats, slots = Env.run(env, 65, sigs, masks, mode=1, **switches)
+        assert res == expect, switches
+        assert stats == [2, 1, 60], switches
+        # slot 8, the hoisted chunk legs' own interval, tells the schedules apart
+        assert (slots[8] > 0) == bool(switches.get("early")), switches
+
+
 def test_two_calls_agree(env):
     sigs = list(env.sigs)
     sigs[100] = env.sigs[101]
@@ -187,15 +139,10 @@ def test_two_calls_agree(env):
 def test_seal_verify_takes_the_combined_path(env):
     blobs = b"".join(env.sigs[j] + env.masks[j] for j in range(65))
     core = env.core
-    core.set_agg_verify_mode(1)
-    core.set_aggrlc_threshold(1)
-    try:
+    with core.aggrlc_switches(mode=1, threshold=1):
         res = env.committee.batch_seal_verify(blobs, 96 + env.bmlen,
                                               b"".join(env.msgs[:65]), env.mlen, 65)
         stats = core.aggrlc_last_stats()
-    finally:
-        core.set_agg_verify_mode(-1)
-        core.set_aggrlc_threshold(-1)
     assert res == [1] * 65
     assert stats == [2, 0, 0]
 

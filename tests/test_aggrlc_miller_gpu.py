@@ -11,7 +11,6 @@ arguments) and 2 (Jacobian arguments, product inside the Miller kernel), each
 hoisted and not, agree with the CPU oracle item for item and report the same
 core.aggrlc_last_stats()."""
 import os
-import random
 import sys
 
 import pytest
@@ -19,23 +18,11 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-pytestmark = pytest.mark.gpu
-
 import arith_cases as ac  # noqa: E402
+from aggrlc_env import BAD, Env, _chunks, gpu_marks, init_core  # noqa: E402
 from oracle import pyref as pr  # noqa: E402
 
-
-def _gpu_available():
-    try:
-        from harmony_amd import core
-        return core.device_count() > 0
-    except Exception:
-        return False
-
-
-if not os.environ.get("HBLS_FORCE_GPU_TESTS"):
-    pytestmark = [pytest.mark.gpu,
-                  pytest.mark.skipif(not _gpu_available(), reason="no AMD GPU")]
+pytestmark = gpu_marks()
 
 P = ac.P
 LEVELS = (0, 1, 2)
@@ -43,9 +30,7 @@ LEVELS = (0, 1, 2)
 
 @pytest.fixture(scope="module")
 def core():
-    from harmony_amd import core as c
-    c.init(-1 if c.device_count() == 0 else 0)
-    return c
+    return init_core()
 
 
 # ------------------------------------------------------------------ the probe
@@ -110,65 +95,17 @@ def test_wave_prod(core):
 
 
 # ------------------------------------------------------------------ end to end
-N = 64                      # committee
 BATCHES = [1, 63, 64, 65, 129, 130]
 TOTAL = max(BATCHES)
-BAD = -1                    # any negative code (the oracle and the library number them apart)
 
 
-def _norm(res):
-    return [BAD if v < 0 else v for v in res]
-
-
-class _Env:
-    """64 keys and 130 valid (mask, message, aggregate signature) items plus
-    the forged signature the tests swap in — built once, never modified"""
-
-    def __init__(self, capi, core):
-        self.core = core
-        self.capi = capi
-        rng = random.Random(8)
-        sk = [pr.synth_sk(300 + i) for i in range(N)]
-        self.pks = core.batch_pk_from_sk(b"".join(pr.fr_serialize(k) for k in sk), N)
-        self.committee = core.Committee(self.pks, N)
-        self.oracle = capi.Committee(self.pks, N)
-        self.bmlen = (N + 7) // 8
-        self.masks, self.msgs, agg_sk = [], [], []
-        for j in range(TOTAL):
-            signers = rng.sample(range(N), rng.randrange(1, N + 1))
-            bm = bytearray(self.bmlen)
-            for i in signers:
-                bm[i >> 3] |= 1 << (i & 7)
-            self.masks.append(bytes(bm))
-            self.msgs.append(pr.construct_commit_payload(j, pr.synth_msg(500 + j), j + 1))
-            agg_sk.append(sum(sk[i] for i in signers) % pr.R)
-        self.mlen = len(self.msgs[0])
-        cat = core.batch_sign(b"".join(pr.fr_serialize(k) for k in agg_sk),
-                              b"".join(self.msgs), self.mlen, TOTAL)
-        self.sigs = [cat[96 * j:96 * (j + 1)] for j in range(TOTAL)]
-        self.D = capi.sign_hash(pr.fr_serialize(pr.synth_sk(999)), self.msgs[0])
-        assert core.aggrlc_chunk_size() == 64
-
+class _Env(Env):
     def configured(self, level, early, call):
         """(results, stats, stage slots 5 and 8) of one call on the combined
         path with the chunk-level leg under the setting"""
-        core = self.core
-        core.set_agg_verify_mode(1)
-        core.set_aggrlc_threshold(1)
-        core.set_aggrlc_sigleg(1)
-        core.set_aggrlc_early(early)
-        core.set_aggrlc_miller(level)
-        try:
-            res = call()
-            stats = core.aggrlc_last_stats()
-            slots = (core.last_stage_ns(5), core.last_stage_ns(8))
-        finally:
-            core.set_agg_verify_mode(-1)
-            core.set_aggrlc_threshold(-1)
-            core.set_aggrlc_sigleg(-1)
-            core.set_aggrlc_early(-1)
-            core.set_aggrlc_miller(-1)
-        return _norm(res), stats, slots
+        res, stats, slots = super().configured(call, mode=1, sigleg=1, early=early,
+                                               miller=level)
+        return res, stats, (slots[5], slots[8])
 
     def check_call(self, call, expect, hoists=True):
         """every level, hoisted and not: results == expect, equal stats, the
@@ -198,21 +135,14 @@ class _Env:
         return stats
 
     def check(self, batch, expect, sigs=None, masks=None):
-        sigs = self.sigs if sigs is None else sigs
-        masks = self.masks if masks is None else masks
-        args = (b"".join(masks[:batch]), b"".join(sigs[:batch]),
-                b"".join(self.msgs[:batch]), self.mlen, batch)
-        assert _norm(self.oracle.batch_agg_verify(*args)) == expect
+        args = self.args(batch, sigs, masks)
+        assert self.oracle_run(batch, sigs, masks) == expect
         return self.check_call(lambda: self.committee.batch_agg_verify(*args), expect)
 
 
 @pytest.fixture(scope="module")
 def env(oracle_lib, core):
-    return _Env(oracle_lib, core)
-
-
-def _chunks(batch):
-    return (batch + 63) // 64
+    return _Env(oracle_lib, core, seed=8)
 
 
 @pytest.mark.parametrize("batch", BATCHES)
@@ -279,9 +209,7 @@ def test_undecodable_signature(env):
 
 def test_cancelling_pair_across_chunks(env):
     a, b = 10, 70
-    sigs = list(env.sigs)
-    sigs[a] = env.capi.g2_add(env.sigs[a], env.D)
-    sigs[b] = env.capi.g2_add(env.sigs[b], env.D, sub=True)
+    sigs = env.cancelling(a, b)
     expect = [1] * TOTAL
     expect[a] = expect[b] = 0
     assert env.check(TOTAL, expect, sigs=sigs) == [3, 2, 128]
@@ -298,26 +226,8 @@ def test_seal_verify(env):
 def test_ctxset_seal_verify_two_committees(env):
     """one call over two committees (the second lists the same keys in reverse
     order, so its items carry the mirrored mask); this entry hoists nothing"""
-    core = env.core
-    pk = [env.pks[48 * i:48 * (i + 1)] for i in range(N)]
-    second = core.Committee(b"".join(reversed(pk)), N)
-    cs = core.ContextSet([env.committee, second])
-
-    def mirrored(mask):
-        out = bytearray(env.bmlen)
-        for i in range(N):
-            if mask[i >> 3] >> (i & 7) & 1:
-                out[(N - 1 - i) >> 3] |= 1 << ((N - 1 - i) & 7)
-        return bytes(out)
-
-    n = 66
-    idx = [j & 1 for j in range(n)]
-    sigs = list(env.sigs[:n])
-    sigs[65] = env.sigs[0]
-    blobs = [sigs[j] + (mirrored(env.masks[j]) if idx[j] else env.masks[j]) for j in range(n)]
-    want = [1] * n
-    want[65] = 0
-    call = lambda: cs.seal_verify(idx, blobs, env.msgs[:n])  # noqa: E731
+    cs, idx, blobs, msgs, want = env.two_committees()
+    call = lambda: cs.seal_verify(idx, blobs, msgs)  # noqa: E731
     assert env.check_call(call, want, hoists=False) == [2, 1, 2]
 
 
@@ -326,10 +236,7 @@ def test_setter_rejects(env, level):
     """a rejected value changes nothing: the call after it runs and agrees"""
     core = env.core
     args = (b"".join(env.masks[:3]), b"".join(env.sigs[:3]), b"".join(env.msgs[:3]), env.mlen, 3)
-    core.set_agg_verify_mode(1)
-    core.set_aggrlc_threshold(1)
-    core.set_aggrlc_sigleg(1)
-    try:
+    with core.aggrlc_switches(mode=1, threshold=1, sigleg=1, miller=-1):
         for keep in LEVELS:
             core.set_aggrlc_miller(keep)
             with pytest.raises(ValueError):
@@ -337,8 +244,3 @@ def test_setter_rejects(env, level):
             assert env.committee.batch_agg_verify(*args) == [1, 1, 1]
             assert core.aggrlc_last_stats() == [1, 0, 0]
             assert core.last_stage_ns(5) > 0
-    finally:
-        core.set_agg_verify_mode(-1)
-        core.set_aggrlc_threshold(-1)
-        core.set_aggrlc_sigleg(-1)
-        core.set_aggrlc_miller(-1)

@@ -9,7 +9,6 @@ End to end: combined path with the signature leg per chunk (leg 1), per item
 (leg 0), the exact path (mode 0) and the CPU oracle agree item for item, and
 the two legs report the same core.aggrlc_last_stats()."""
 import os
-import random
 import sys
 
 import pytest
@@ -17,33 +16,19 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-pytestmark = pytest.mark.gpu
-
 import arith_cases as ac  # noqa: E402
+from aggrlc_env import BAD, Env, _chunks, gpu_marks, init_core  # noqa: E402
 from oracle import pyref as pr  # noqa: E402
 from test_aggrlc_sigleg_formulas import ALL_DIGITS, PROBE_SCALARS, recode64  # noqa: E402
 
-
-def _gpu_available():
-    try:
-        from harmony_amd import core
-        return core.device_count() > 0
-    except Exception:
-        return False
-
-
-if not os.environ.get("HBLS_FORCE_GPU_TESTS"):
-    pytestmark = [pytest.mark.gpu,
-                  pytest.mark.skipif(not _gpu_available(), reason="no AMD GPU")]
+pytestmark = gpu_marks()
 
 P = ac.P
 
 
 @pytest.fixture(scope="module")
 def core():
-    from harmony_amd import core as c
-    c.init(-1 if c.device_count() == 0 else 0)
-    return c
+    return init_core()
 
 
 # ------------------------------------------------------------------ the probe
@@ -103,65 +88,16 @@ def test_miller1_fe(core):
 
 
 # ------------------------------------------------------------------ end to end
-N = 64                      # committee
 BATCHES = [1, 63, 64, 65, 129, 130]
 TOTAL = max(BATCHES)
-BAD = -1                    # any negative code (the oracle and the library number them apart)
 
 
-def _norm(res):
-    return [BAD if v < 0 else v for v in res]
-
-
-class _Env:
-    """64 keys and 130 valid (mask, message, aggregate signature) items plus
-    the forged signature the tests swap in — built once, never modified"""
-
-    def __init__(self, capi, core):
-        self.core = core
-        self.capi = capi
-        rng = random.Random(6)
-        sk = [pr.synth_sk(300 + i) for i in range(N)]
-        self.pks = core.batch_pk_from_sk(b"".join(pr.fr_serialize(k) for k in sk), N)
-        self.committee = core.Committee(self.pks, N)
-        self.oracle = capi.Committee(self.pks, N)
-        self.bmlen = (N + 7) // 8
-        self.masks, self.msgs, agg_sk = [], [], []
-        for j in range(TOTAL):
-            signers = rng.sample(range(N), rng.randrange(1, N + 1))
-            bm = bytearray(self.bmlen)
-            for i in signers:
-                bm[i >> 3] |= 1 << (i & 7)
-            self.masks.append(bytes(bm))
-            self.msgs.append(pr.construct_commit_payload(j, pr.synth_msg(500 + j), j + 1))
-            agg_sk.append(sum(sk[i] for i in signers) % pr.R)
-        self.mlen = len(self.msgs[0])
-        cat = core.batch_sign(b"".join(pr.fr_serialize(k) for k in agg_sk),
-                              b"".join(self.msgs), self.mlen, TOTAL)
-        self.sigs = [cat[96 * j:96 * (j + 1)] for j in range(TOTAL)]
-        self.D = capi.sign_hash(pr.fr_serialize(pr.synth_sk(999)), self.msgs[0])
-        assert core.aggrlc_chunk_size() == 64
-
+class _Env(Env):
     def configured(self, mode, leg, call):
-        core = self.core
-        core.set_agg_verify_mode(mode)
-        core.set_aggrlc_threshold(1)
-        core.set_aggrlc_sigleg(leg)
-        try:
-            res = call()
-            stats = core.aggrlc_last_stats()
-        finally:
-            core.set_agg_verify_mode(-1)
-            core.set_aggrlc_threshold(-1)
-            core.set_aggrlc_sigleg(-1)
-        return _norm(res), stats
+        return super().configured(call, mode=mode, sigleg=leg)[:2]
 
     def run(self, mode, leg, batch, sigs=None, masks=None):
-        sigs = self.sigs if sigs is None else sigs
-        masks = self.masks if masks is None else masks
-        return self.configured(mode, leg, lambda: self.committee.batch_agg_verify(
-            b"".join(masks[:batch]), b"".join(sigs[:batch]),
-            b"".join(self.msgs[:batch]), self.mlen, batch))
+        return super().run(batch, sigs, masks, mode=mode, sigleg=leg)[:2]
 
     def check(self, batch, expect, sigs=None, masks=None):
         """leg 1 == leg 0 == mode 0 == oracle == expect, and the two legs'
@@ -173,22 +109,14 @@ class _Env:
         assert r1 == expect
         assert r0 == expect
         assert rx == expect
-        sigs = self.sigs if sigs is None else sigs
-        masks = self.masks if masks is None else masks
-        assert _norm(self.oracle.batch_agg_verify(
-            b"".join(masks[:batch]), b"".join(sigs[:batch]),
-            b"".join(self.msgs[:batch]), self.mlen, batch)) == expect
+        assert self.oracle_run(batch, sigs, masks) == expect
         assert s1 == s0
         return s1
 
 
 @pytest.fixture(scope="module")
 def env(oracle_lib, core):
-    return _Env(oracle_lib, core)
-
-
-def _chunks(batch):
-    return (batch + 63) // 64
+    return _Env(oracle_lib, core, seed=6)
 
 
 @pytest.mark.parametrize("batch", BATCHES)
@@ -207,27 +135,20 @@ def test_one_wrong_signature(env, batch, bad):
     assert stats == [_chunks(batch), 1, min(batch, first + 64) - first]
 
 
-def _cancelling(env, a, b):
-    sigs = list(env.sigs)
-    sigs[a] = env.capi.g2_add(env.sigs[a], env.D)
-    sigs[b] = env.capi.g2_add(env.sigs[b], env.D, sub=True)
-    return sigs
-
-
 def test_cancelling_pair_in_one_chunk(env):
     """sig_a + D and sig_b - D: the unweighted sum of the two signatures is
     that of the valid ones, the weighted one must not be"""
     a, b = 3, 41
     expect = [1] * 65
     expect[a] = expect[b] = 0
-    assert env.check(65, expect, sigs=_cancelling(env, a, b)) == [2, 1, 64]
+    assert env.check(65, expect, sigs=env.cancelling(a, b)) == [2, 1, 64]
 
 
 def test_cancelling_pair_across_chunks(env):
     a, b = 10, 70
     expect = [1] * TOTAL
     expect[a] = expect[b] = 0
-    assert env.check(TOTAL, expect, sigs=_cancelling(env, a, b)) == [3, 2, 128]
+    assert env.check(TOTAL, expect, sigs=env.cancelling(a, b)) == [3, 2, 128]
 
 
 def test_undecodable_signature(env):
@@ -273,26 +194,8 @@ def test_seal_verify(env):
 def test_ctxset_seal_verify_two_committees(env):
     """one call over two committees: the second lists the same keys in
     reverse order, so its items carry the mirrored mask"""
-    core = env.core
-    pk = [env.pks[48 * i:48 * (i + 1)] for i in range(N)]
-    second = core.Committee(b"".join(reversed(pk)), N)
-    cs = core.ContextSet([env.committee, second])
-
-    def mirrored(mask):
-        out = bytearray(env.bmlen)
-        for i in range(N):
-            if mask[i >> 3] >> (i & 7) & 1:
-                out[(N - 1 - i) >> 3] |= 1 << ((N - 1 - i) & 7)
-        return bytes(out)
-
-    n = 66
-    idx = [j & 1 for j in range(n)]
-    sigs = list(env.sigs[:n])
-    sigs[65] = env.sigs[0]
-    blobs = [sigs[j] + (mirrored(env.masks[j]) if idx[j] else env.masks[j]) for j in range(n)]
-    call = lambda: cs.seal_verify(idx, blobs, env.msgs[:n])  # noqa: E731
-    want = [1] * n
-    want[65] = 0
+    cs, idx, blobs, msgs, want = env.two_committees()
+    call = lambda: cs.seal_verify(idx, blobs, msgs)  # noqa: E731
     r1, s1 = env.configured(1, 1, call)
     r0, s0 = env.configured(1, 0, call)
     rx, _ = env.configured(0, -1, call)
@@ -305,14 +208,11 @@ def test_setter_rejects(env, leg):
     core = env.core
     sigs = list(env.sigs)
     sigs[1] = env.sigs[2]
-    core.set_aggrlc_sigleg(1)
-    try:
+    with core.aggrlc_switches(mode=1, threshold=1, sigleg=1):
         with pytest.raises(ValueError):
             core.set_aggrlc_sigleg(leg)
         # the rejected call changed nothing: leg 1 still runs, so a failing
         # chunk is found through its chunk entry
-        core.set_agg_verify_mode(1)
-        core.set_aggrlc_threshold(1)
         res = env.committee.batch_agg_verify(
             b"".join(env.masks[:3]), b"".join(sigs[:3]), b"".join(env.msgs[:3]), env.mlen, 3)
         assert res == [1, 0, 1]
@@ -322,7 +222,3 @@ def test_setter_rejects(env, leg):
             b"".join(env.masks[:3]), b"".join(sigs[:3]), b"".join(env.msgs[:3]), env.mlen, 3)
         assert res == [1, 0, 1]
         assert core.last_stage_ns(7) == 0
-    finally:
-        core.set_agg_verify_mode(-1)
-        core.set_aggrlc_threshold(-1)
-        core.set_aggrlc_sigleg(-1)

@@ -11,71 +11,27 @@ put verdicts at the wrong indices.
 Shapes: 64 items = one chunk and 15 dummy sub-items in its block; 1089 items
 = 18 chunks, two blocks, the last chunk holding one item."""
 import os
-import random
 import sys
 
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-pytestmark = pytest.mark.gpu
+from aggrlc_env import BAD, CHUNK, N, Env, _chunks, _norm, gpu_marks  # noqa: E402
 
-from oracle import pyref as pr  # noqa: E402
+pytestmark = gpu_marks()
 
-
-def _gpu_available():
-    try:
-        from harmony_amd import core
-        return core.device_count() > 0
-    except Exception:
-        return False
-
-
-if not os.environ.get("HBLS_FORCE_GPU_TESTS"):
-    pytestmark = [pytest.mark.gpu,
-                  pytest.mark.skipif(not _gpu_available(), reason="no AMD GPU")]
-
-N = 64                      # committee
 TOTAL = 1089                # 17 * 64 + 1
-CHUNK = 64
-BAD = -1                    # any negative code (the oracle and the library number them apart)
 
 
-def _norm(res):
-    return [BAD if v < 0 else v for v in res]
+class _Env(Env):
+    """1089 valid items.  The oracle's verdicts on them are computed once; an
+    altered input set costs one oracle run over the altered items only (every
+    item is its own check, so the others keep their verdicts)."""
 
-
-class _Env:
-    """64 keys and 1089 valid (mask, message, aggregate signature) items —
-    built once, never modified; tests work on copies of the lists.  The
-    oracle's verdicts on the valid items are computed once; an altered input
-    set costs one oracle run over the altered items only (every item is its
-    own check, so the others keep their verdicts)."""
-
-    def __init__(self, capi):
-        from harmony_amd import core
-        self.core = core
-        self.capi = capi
-        rng = random.Random(11)
-        sk = [pr.synth_sk(700 + i) for i in range(N)]
-        self.pks = core.batch_pk_from_sk(b"".join(pr.fr_serialize(k) for k in sk), N)
-        self.committee = core.Committee(self.pks, N)
-        self.oracle = capi.Committee(self.pks, N)
-        self.bmlen = (N + 7) // 8
-        self.masks, self.msgs, agg_sk = [], [], []
-        for j in range(TOTAL):
-            signers = rng.sample(range(N), rng.randrange(1, N + 1))
-            bm = bytearray(self.bmlen)
-            for i in signers:
-                bm[i >> 3] |= 1 << (i & 7)
-            self.masks.append(bytes(bm))
-            self.msgs.append(pr.construct_commit_payload(j, pr.synth_msg(900 + j), j + 1))
-            agg_sk.append(sum(sk[i] for i in signers) % pr.R)
-        self.mlen = len(self.msgs[0])
-        cat = core.batch_sign(b"".join(pr.fr_serialize(k) for k in agg_sk),
-                              b"".join(self.msgs), self.mlen, TOTAL)
-        self.sigs = [cat[96 * j:96 * (j + 1)] for j in range(TOTAL)]
-        assert core.aggrlc_chunk_size() == CHUNK
+    def __init__(self, capi, core):
+        super().__init__(capi, core, seed=11, total=TOTAL, sk_base=700, msg_base=900)
         self.base = self._oracle(self.masks, self.sigs, self.msgs)
         assert self.base == [1] * TOTAL
 
@@ -101,22 +57,7 @@ class _Env:
     def run(self, mode, batch, sigs=None, msgs=None, final=-1):
         """(normalised verdicts, stats) of one batch_agg_verify call over the
         first `batch` items in the given mode and final kernel"""
-        core = self.core
-        sigs = self.sigs if sigs is None else sigs
-        msgs = self.msgs if msgs is None else msgs
-        core.set_agg_verify_mode(mode)
-        core.set_aggrlc_threshold(1)
-        core.set_aggrlc_final(final)
-        try:
-            res = self.committee.batch_agg_verify(
-                b"".join(self.masks[:batch]), b"".join(sigs[:batch]),
-                b"".join(msgs[:batch]), self.mlen, batch)
-            stats = core.aggrlc_last_stats()
-        finally:
-            core.set_agg_verify_mode(-1)
-            core.set_aggrlc_threshold(-1)
-            core.set_aggrlc_final(-1)
-        return _norm(res), stats
+        return super().run(batch, sigs, None, msgs, mode=mode, final=final)[:2]
 
     def check(self, batch, expect, sigs=None, msgs=None, changed=()):
         """mode 1 == mode 0 == oracle == expect, item for item; returns mode
@@ -132,11 +73,8 @@ class _Env:
 
 @pytest.fixture(scope="module")
 def env(oracle_lib):
-    return _Env(oracle_lib)
-
-
-def _chunks(batch):
-    return (batch + CHUNK - 1) // CHUNK
+    from harmony_amd import core
+    return _Env(oracle_lib, core)
 
 
 # ---- the final kernels alone
@@ -259,16 +197,11 @@ def test_seal_and_quorum_entries_unchanged(env):
     qc.set_quorum()
     out = {}
     for mode in (0, 1):
-        core.set_agg_verify_mode(mode)
-        core.set_aggrlc_threshold(1)
-        try:
+        with core.aggrlc_switches(mode=mode, threshold=1):
             seal = env.committee.batch_seal_verify(blobs, 96 + env.bmlen, msgs,
                                                    env.mlen, TOTAL)
             quorum = qc.batch_agg_verify_quorum(b"".join(env.masks), b"".join(sigs),
                                                 msgs, env.mlen, TOTAL)
-        finally:
-            core.set_agg_verify_mode(-1)
-            core.set_aggrlc_threshold(-1)
         out[mode] = (seal, quorum)
     assert out[1] == out[0]
     seal, quorum = out[1]

@@ -344,17 +344,12 @@ def test_both_pairing_modes(env):
     core = env.core
     for name, idx, blobs, want, failing in _cases(env):
         eligible = sum(1 for r in want if r != BADINPUT)
-        try:
-            core.set_agg_verify_mode(0)
+        with core.aggrlc_switches(mode=0):
             r0 = env.ctxset.seal_verify(idx, blobs, env.msgs)
             s0 = core.aggrlc_last_stats()
-            core.set_agg_verify_mode(1)
-            core.set_aggrlc_threshold(1)
+        with core.aggrlc_switches(mode=1, threshold=1):
             r1 = env.ctxset.seal_verify(idx, blobs, env.msgs)
             s1 = core.aggrlc_last_stats()
-        finally:
-            core.set_agg_verify_mode(-1)
-            core.set_aggrlc_threshold(-1)
         assert r0 == want and r1 == want, name
         assert s0 == [0, 0, 0], name
         # chunks are formed over the mixed batch, malformed items left out
@@ -414,14 +409,9 @@ def test_quorum_gate(env):
     idx2[-2] = NCTX
     want2[-2] = BADINPUT
     for mode in (0, 1):
-        try:
-            core.set_agg_verify_mode(mode)
-            core.set_aggrlc_threshold(1)
+        with core.aggrlc_switches(mode=mode, threshold=1):
             res = env.ctxset.seal_verify(idx2, blobs2, msgs, quorum=True)
             stats = core.aggrlc_last_stats()
-        finally:
-            core.set_agg_verify_mode(-1)
-            core.set_aggrlc_threshold(-1)
         assert res == want2, mode
         if mode == 1:
             # quorumless and malformed items never reach a chunk

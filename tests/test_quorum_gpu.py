@@ -274,29 +274,19 @@ class _Env:
     def run(self, mode, fn, batch, sigs, masks):
         """(results, stats) of committee.<fn> over the first `batch` items"""
         core = self.core
-        core.set_agg_verify_mode(mode)
-        core.set_aggrlc_threshold(1)
-        try:
+        with core.aggrlc_switches(mode=mode, threshold=1):
             res = getattr(self.committee, fn)(
                 b"".join(masks[:batch]), b"".join(sigs[:batch]),
                 b"".join(self.msgs[:batch]), self.mlen, batch)
             stats = core.aggrlc_last_stats()
-        finally:
-            core.set_agg_verify_mode(-1)
-            core.set_aggrlc_threshold(-1)
         return res, stats
 
     def seal(self, mode, batch, sigs, masks):
         core = self.core
         blobs = b"".join(sigs[j] + masks[j] for j in range(batch))
-        core.set_agg_verify_mode(mode)
-        core.set_aggrlc_threshold(1)
-        try:
+        with core.aggrlc_switches(mode=mode, threshold=1):
             return self.committee.batch_seal_verify_quorum(
                 blobs, 96 + self.bmlen, b"".join(self.msgs[:batch]), self.mlen, batch)
-        finally:
-            core.set_agg_verify_mode(-1)
-            core.set_aggrlc_threshold(-1)
 
     def oracle_run(self, batch, sigs, masks):
         return self.oracle.batch_agg_verify(

@@ -90,12 +90,7 @@ def run_step0(args):
     out = {"what": "leg 1 with the chunk entries inside the Miller kernel; sizes alternate in "
                    "one process after a warm-up round; miller_ms = hbls_last_stage_ns(4)",
            "committee": n, "rounds": args.rounds, "version": core.version(), "sizes": {}}
-    core.set_agg_verify_mode(1)
-    core.set_aggrlc_threshold(1)
-    core.set_aggrlc_sigleg(1)
-    if hasattr(core, "set_aggrlc_early"):
-        core.set_aggrlc_early(0)
-    try:
+    with core.aggrlc_switches(mode=1, threshold=1, sigleg=1, early=0):
         rec = {b: [] for b in sizes}
         for rnd in range(args.rounds + 1):
             k = rnd % len(sizes)
@@ -118,12 +113,6 @@ def run_step0(args):
         out["gap_at_least_3x_spread"] = bool(gap >= 3 * wider)
         print(json.dumps({k: out[k] for k in ("gap_ms", "wider_spread_ms",
                                               "gap_at_least_3x_spread")}), flush=True)
-    finally:
-        core.set_agg_verify_mode(-1)
-        core.set_aggrlc_threshold(-1)
-        core.set_aggrlc_sigleg(-1)
-        if hasattr(core, "set_aggrlc_early"):
-            core.set_aggrlc_early(-1)
     return out
 
 
@@ -138,10 +127,8 @@ def run_sweep(args):
     sizes = [int(s) for s in args.sizes.split(",") if int(s) <= B]
     out = {"committee": n, "batch": B, "rounds": args.rounds, "version": core.version(),
            "legs": [name for name, _, _ in SWEEP_LEGS], "slots": list(SLOT_NAMES), "sizes": {}}
-    core.set_agg_verify_mode(1)
-    core.set_aggrlc_threshold(1)
-    core.set_aggrlc_sigleg(1)
-    try:
+    # the legs set early and chunkleg themselves; everything goes back on the way out
+    with core.aggrlc_switches(mode=1, threshold=1, sigleg=1, early=-1, chunkleg=-1):
         for b in sizes:
             rec = {name: [] for name, _, _ in SWEEP_LEGS}
             for rnd in range(args.rounds + 1):          # round 0 warms up
@@ -191,12 +178,6 @@ def run_sweep(args):
                               "dirty_stats": dirty["stats"], "dirty_bad": dirty["bad"],
                               "dirty_extra_wall_ms": round(dirty["wall_ms"] - good["wall_ms"], 2)}),
                   flush=True)
-    finally:
-        core.set_agg_verify_mode(-1)
-        core.set_aggrlc_threshold(-1)
-        core.set_aggrlc_sigleg(-1)
-        core.set_aggrlc_early(-1)
-        core.set_aggrlc_chunkleg(-1)
     return out
 
 

@@ -46,10 +46,8 @@ def run_sweep(args):
            "what": "batch_agg_verify on the combined path, chunk-level leg, the early rule at "
                    "its default; levels alternate in one process after a warm-up round",
            "sizes": {}}
-    core.set_agg_verify_mode(1)
-    core.set_aggrlc_threshold(1)
-    core.set_aggrlc_sigleg(1)
-    try:
+    # the legs set the level themselves; everything goes back on the way out
+    with core.aggrlc_switches(mode=1, threshold=1, sigleg=1, miller=-1):
         for b in sizes:
             rec = {_name(v): [] for v in LEVELS}
             for rnd in range(args.rounds + 1):          # round 0 warms up
@@ -104,11 +102,6 @@ def run_sweep(args):
                               "dirty_stats": dirty["stats"], "dirty_bad": dirty["bad"],
                               "dirty_extra_wall_ms": round(dirty["wall_ms"] - good["wall_ms"], 2)}),
                   flush=True)
-    finally:
-        core.set_agg_verify_mode(-1)
-        core.set_aggrlc_threshold(-1)
-        core.set_aggrlc_sigleg(-1)
-        core.set_aggrlc_miller(-1)
     return out
 
 

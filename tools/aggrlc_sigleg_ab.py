@@ -134,8 +134,8 @@ def run_sweep(args):
     sizes = [int(s) for s in args.sizes.split(",") if int(s) <= B]
     out = {"committee": n, "batch": B, "rounds": args.rounds, "version": core.version(),
            "legs": [name for name, _, _ in SWEEP_LEGS], "sizes": {}}
-    core.set_aggrlc_threshold(1)
-    try:
+    # the legs set mode and sigleg themselves; everything goes back on the way out
+    with core.aggrlc_switches(threshold=1, mode=-1, sigleg=-1):
         for b in sizes:
             rec = {name: [] for name, _, _ in SWEEP_LEGS}
             for rnd in range(args.rounds + 1):          # round 0 warms up
@@ -172,10 +172,6 @@ def run_sweep(args):
             print(json.dumps({"one_bad_item": name, "stats": bad["stats"], "bad": bad["bad"],
                               "extra_wall_ms": round(bad["wall_ms"] - good["wall_ms"], 2)}),
                   flush=True)
-    finally:
-        core.set_agg_verify_mode(-1)
-        core.set_aggrlc_threshold(-1)
-        core.set_aggrlc_sigleg(-1)
     return out
 
 

@@ -70,8 +70,8 @@ def main():
     out = {"committee": n, "batch": B, "rounds": args.rounds, "version": core.version(),
            "legs": [name for name, _, _ in LEGS], "sizes": {}}
 
-    core.set_aggrlc_threshold(1)
-    try:
+    # the legs set mode and final themselves; everything goes back on the way out
+    with core.aggrlc_switches(threshold=1, mode=-1, final=-1):
         for b in sizes:
             rec = {name: [] for name, _, _ in LEGS}
             for rnd in range(args.rounds + 1):          # round 0 warms up
@@ -96,10 +96,6 @@ def main():
                                                   round(max(v["wall_ms"]), 2),
                                                   round(statistics.median(v["final_ms"]), 2)]
                                              for k, v in summary.items()}}), flush=True)
-    finally:
-        core.set_agg_verify_mode(-1)
-        core.set_aggrlc_threshold(-1)
-        core.set_aggrlc_final(-1)
 
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
