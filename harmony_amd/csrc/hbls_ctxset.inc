@@ -484,24 +484,11 @@ extern "C" int hbls_batch_seal_verify_ctx(const hbls_ctxset_t *s, const uint32_t
         l_sig = gsig.as<uint8_t>();
         l_msg = gmsg.as<uint8_t>();
     }
-    int nb = (int)((nlive + 63) / 64);
-    if ((int)nlive <= coop_threshold()) {
-        LAUNCH_COOP(k_hash_to_g2_coop, nlive, l_msg, CX_MSG_SLOT, dhm.as<g2_t>(),
-                    dhok.as<int32_t>(), (int)nlive, g_fast_cofactor);
-    } else {
-        hipLaunchKernelGGL(k_hash_to_g2, dim3(nb), dim3(64), 0, 0,
-                           l_msg, CX_MSG_SLOT, dhm.as<g2_t>(), dhok.as<int32_t>(),
-                           (int)nlive, g_fast_cofactor);
-    }
+    /* every stage from here dispatches on nlive, not on batch */
+    launch_hash_to_g2(l_msg, CX_MSG_SLOT, dhm.as<g2_t>(), dhok.as<int32_t>(), nlive);
     (void)hipEventRecord(ev[3], 0);
     (void)hipEventRecord(ev[4], 0);
-    if ((int)nlive <= coop_threshold()) {
-        LAUNCH_COOP(k_g2_decompress_coop, nlive, l_sig, dsaff.as<g2aff_t>(),
-                    dsflags.as<int32_t>(), (int)nlive);
-    } else {
-        hipLaunchKernelGGL(k_g2_decompress, dim3(nb), dim3(64), 0, 0,
-                           l_sig, dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)nlive);
-    }
+    launch_g2_decompress(l_sig, dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), nlive);
     (void)hipEventRecord(ev[5], 0);
     (void)hipEventRecord(ev[0], 0);
     hipLaunchKernelGGL(k_ctx_mask_aggregate, dim3((uint32_t)nlive), dim3(64), 0, 0,

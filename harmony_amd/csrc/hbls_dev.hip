@@ -2462,6 +2462,8 @@ struct DevBuf {
     void *p = nullptr;
     hipError_t err = hipSuccess;
     explicit DevBuf(size_t n) { err = hipMalloc(&p, n ? n : 1); }
+    /* a buffer that only some callers of a shared body need: none unless wanted */
+    DevBuf(size_t n, bool wanted) { if (wanted) err = hipMalloc(&p, n ? n : 1); }
     ~DevBuf() { if (p) hipFree(p); }
     template <typename T> T *as() const { return (T *)p; }
 };
@@ -2557,7 +2559,7 @@ template <int N> struct EventSet {
 };
 
 struct Timer {
-    hipEvent_t a, b;
+    hipEvent_t a = nullptr, b = nullptr;
     Timer() { hipEventCreate(&a); hipEventCreate(&b); hipEventRecord(a, 0); }
     void stop_and_store() {
         hipEventRecord(b, 0);
@@ -2565,9 +2567,26 @@ struct Timer {
         float ms = 0;
         hipEventElapsedTime(&ms, a, b);
         g_last_ns = (uint64_t)(ms * 1e6);
-        hipEventDestroy(a); hipEventDestroy(b);
+        destroy();
+    }
+    /* a caller that returns before stop_and_store() leaves both alive */
+    ~Timer() { destroy(); }
+    void destroy() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        a = b = nullptr;
     }
 };
+
+/* the tail of the batch entries that report per-item ok-flags: download them,
+ * HBLS_ERR_BADINPUT if any is 0 */
+static int check_ok_flags(const int32_t *d_ok, size_t batch) {
+    std::vector<int32_t> ok(batch);
+    HIP_OK(hipMemcpy(ok.data(), d_ok, batch * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < batch; i++)
+        if (!ok[i]) return HBLS_ERR_BADINPUT;
+    return HBLS_OK;
+}
 
 extern "C" int hbls_batch_pk_from_sk(const uint8_t *sks32, size_t batch, uint8_t *pks48) {
     int rc = require_gpu();
@@ -2582,11 +2601,7 @@ extern "C" int hbls_batch_pk_from_sk(const uint8_t *sks32, size_t batch, uint8_t
     tm.stop_and_store();
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(pks48, dpk.p, batch * 48, hipMemcpyDeviceToHost));
-    std::vector<int32_t> ok(batch);
-    HIP_OK(hipMemcpy(ok.data(), dok.p, batch * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < batch; i++)
-        if (!ok[i]) return HBLS_ERR_BADINPUT;
-    return HBLS_OK;
+    return check_ok_flags(dok.as<int32_t>(), batch);
 }
 
 extern "C" int hbls_pk_from_sk(const uint8_t sk32[32], uint8_t pk48[48]) {
@@ -2602,6 +2617,7 @@ extern "C" int hbls_batch_hash_to_g2(const uint8_t *msgs, size_t msg_len, size_t
     HIP_OK(hipMemcpy(dm.p, msgs, batch * msg_len, hipMemcpyHostToDevice));
     Timer tm;
     int nb = (int)((batch + 63) / 64);
+    /* exception: no verify stage; the thread-per-item hash whatever the threshold */
     hipLaunchKernelGGL(k_hash_to_g2, dim3(nb), dim3(64), 0, 0,
                        dm.as<uint8_t>(), (int)msg_len, dout.as<g2_t>(), dok.as<int32_t>(),
                        (int)batch, g_fast_cofactor);
@@ -2610,11 +2626,7 @@ extern "C" int hbls_batch_hash_to_g2(const uint8_t *msgs, size_t msg_len, size_t
     tm.stop_and_store();
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(out96s, dser.p, batch * 96, hipMemcpyDeviceToHost));
-    std::vector<int32_t> ok(batch);
-    HIP_OK(hipMemcpy(ok.data(), dok.p, batch * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < batch; i++)
-        if (!ok[i]) return HBLS_ERR_BADINPUT;
-    return HBLS_OK;
+    return check_ok_flags(dok.as<int32_t>(), batch);
 }
 extern "C" int hbls_hash_to_g2(const uint8_t *msg, size_t msg_len, uint8_t out96[96]) {
     return hbls_batch_hash_to_g2(msg, msg_len, 1, out96);
@@ -2636,11 +2648,7 @@ extern "C" int hbls_batch_sign(const uint8_t *sks32, const uint8_t *msgs, size_t
     tm.stop_and_store();
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(sigs96, dsig.p, batch * 96, hipMemcpyDeviceToHost));
-    std::vector<int32_t> ok(batch);
-    HIP_OK(hipMemcpy(ok.data(), dok.p, batch * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < batch; i++)
-        if (!ok[i]) return HBLS_ERR_BADINPUT;
-    return HBLS_OK;
+    return check_ok_flags(dok.as<int32_t>(), batch);
 }
 extern "C" int hbls_sign_hash(const uint8_t sk32[32], const uint8_t *msg, size_t msg_len,
                               uint8_t sig96[96]) {
@@ -2682,33 +2690,6 @@ static int use_batch_affine(void) {
     if (m < 0) { const char *e = getenv("HBLS_BATCH_AFFINE"); m = (e && atoi(e)) ? 1 : 0; }
     return m;
 }
-#ifdef HBLS_RF
-#define HBLS_RF_CASES(nb, ...) \
-    case 1: hipLaunchKernelGGL(k_verify_rf, dim3(nb), dim3(64), 0, 0, __VA_ARGS__); break; \
-    case 2: hipLaunchKernelGGL(HBLS_RF_W2_KERN, dim3(nb), dim3(64), 0, 0, __VA_ARGS__); break; \
-    case 3: hipLaunchKernelGGL(HBLS_RF_W1_KERN, dim3(nb), dim3(64), 0, 0, __VA_ARGS__); break;
-#else
-#define HBLS_RF_CASES(nb, ...)
-#endif
-#define LAUNCH_VERIFY_SCALAR(nb, ...) do { \
-    switch (rf_mode()) { \
-    HBLS_RF_CASES(nb, __VA_ARGS__) \
-    case 4: hipLaunchKernelGGL(k_verify_2p, dim3(nb), dim3(64), 0, 0, __VA_ARGS__); break; \
-    case 5: hipLaunchKernelGGL(k_verify_6, dim3(nb), dim3(64), 0, 0, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL(k_verify, dim3(nb), dim3(64), 0, 0, __VA_ARGS__); break; \
-    } \
-} while (0)
-/* votes through the rf path go: gather (pubs + per-item hm) -> k_verify_rf.
- * gb_pub/gb_hm/gb_ok are caller-allocated DevBufs sized batch. */
-#define LAUNCH_VOTES_SCALAR_RF(nb, table, nn, didx, dhm, dhmidx, dsaff, dsflags, dhok, dres, batch, gb_pub, gb_hm, gb_ok, RFKERN) do { \
-    hipLaunchKernelGGL(k_gather_votes_rf, dim3(nb), dim3(64), 0, 0, \
-                       table, nn, didx, dhm, dhmidx, dhok, \
-                       (gb_pub).as<g1_t>(), (gb_hm).as<g2_t>(), (gb_ok).as<int32_t>(), batch); \
-    hipLaunchKernelGGL(RFKERN, dim3(nb), dim3(64), 0, 0, \
-                       (gb_pub).as<g1_t>(), (gb_hm).as<g2_t>(), dsaff, dsflags, \
-                       (gb_ok).as<int32_t>(), dres, batch); \
-} while (0)
-
 /* coop items-per-block dispatch.  MEASURED (profiles/r02_data/r2g_coopab.log):
  * the 8-item/32-thread variant (38 KB arena, 4 blocks/CU) is WORSE at every
  * batch (e.g. 116 vs 82 ms at 4096, stream 17.9k vs 19.2k msgs/s) — the
@@ -2726,12 +2707,111 @@ static int coop_items(size_t batch) {
     return 16;
 }
 
-#define LAUNCH_COOP(kern, batch, ...) do { \
-    int it_ = coop_items(batch); \
-    int nbc_ = (int)(((batch) + it_ - 1) / it_); \
+/* ---- one launcher per stage of the verify pipelines.  Every
+ * entry point goes through these.  Each takes the wave-cooperative kernel when
+ * the n it is given is at or below coop_threshold() and the thread-per-item
+ * kernel above it, on the null stream; the caller chooses the n. */
+#define LAUNCH_COOP(kern, n, ...) do { \
+    int it_ = coop_items(n); \
+    int nbc_ = (int)(((n) + it_ - 1) / it_); \
     if (it_ == 16) hipLaunchKernelGGL(kern<16>, dim3(nbc_), dim3(64), 0, 0, __VA_ARGS__); \
     else hipLaunchKernelGGL(kern<8>, dim3(nbc_), dim3(32), 0, 0, __VA_ARGS__); \
 } while (0)
+static inline bool coop_wanted(size_t n) { return (int)n <= coop_threshold(); }
+static inline int scalar_blocks(size_t n) { return (int)((n + 63) / 64); }
+
+/* the cooperative hash whatever the threshold: launch_hash_to_g2's first
+ * branch, and what hbls_stream_set_rounds always takes */
+static void launch_hash_to_g2_coop(const uint8_t *d_msg, size_t msg_len, g2_t *d_hm,
+                                   int32_t *d_hok, size_t n) {
+    LAUNCH_COOP(k_hash_to_g2_coop, n, d_msg, (int)msg_len, d_hm, d_hok, (int)n,
+                g_fast_cofactor);
+}
+/* n messages of msg_len bytes -> n hash points and their ok-flags */
+static void launch_hash_to_g2(const uint8_t *d_msg, size_t msg_len, g2_t *d_hm,
+                              int32_t *d_hok, size_t n) {
+    if (coop_wanted(n))
+        launch_hash_to_g2_coop(d_msg, msg_len, d_hm, d_hok, n);
+    else
+        hipLaunchKernelGGL(k_hash_to_g2, dim3(scalar_blocks(n)), dim3(64), 0, 0,
+                           d_msg, (int)msg_len, d_hm, d_hok, (int)n, g_fast_cofactor);
+}
+/* n serialized signatures -> affine points and their flags */
+static void launch_g2_decompress(const uint8_t *d_sig, g2aff_t *d_saff, int32_t *d_sflags,
+                                 size_t n) {
+    if (coop_wanted(n))
+        LAUNCH_COOP(k_g2_decompress_coop, n, d_sig, d_saff, d_sflags, (int)n);
+    else
+        hipLaunchKernelGGL(k_g2_decompress, dim3(scalar_blocks(n)), dim3(64), 0, 0,
+                           d_sig, d_saff, d_sflags, (int)n);
+}
+/* the thread-per-item pairing check, by rf_mode() */
+static void launch_verify_scalar(const g1_t *d_pub, const g2_t *d_hm, const g2aff_t *d_saff,
+                                 const int32_t *d_sflags, const int32_t *d_hok,
+                                 int32_t *d_res, size_t n) {
+    void (*kern)(const g1_t *, const g2_t *, const g2aff_t *, const int32_t *,
+                 const int32_t *, int32_t *, int) = k_verify;
+    switch (rf_mode()) {
+#ifdef HBLS_RF
+    case 1: kern = k_verify_rf; break;
+    case 2: kern = HBLS_RF_W2_KERN; break;
+    case 3: kern = HBLS_RF_W1_KERN; break;
+#endif
+    case 4: kern = k_verify_2p; break;
+    case 5: kern = k_verify_6; break;
+    }
+    hipLaunchKernelGGL(kern, dim3(scalar_blocks(n)), dim3(64), 0, 0,
+                       d_pub, d_hm, d_saff, d_sflags, d_hok, d_res, (int)n);
+}
+/* pairing check of n prepared (key sum, hash point, signature) triples */
+static void launch_verify(const g1_t *d_pub, const g2_t *d_hm, const g2aff_t *d_saff,
+                          const int32_t *d_sflags, const int32_t *d_hok, int32_t *d_res,
+                          size_t n) {
+    if (coop_wanted(n))
+        LAUNCH_COOP(k_verify_coop, n, d_pub, d_hm, d_saff, d_sflags, d_hok, d_res, (int)n);
+    else
+        launch_verify_scalar(d_pub, d_hm, d_saff, d_sflags, d_hok, d_res, n);
+}
+/* gather buffers of the rf votes path: the caller declares one ahead of its
+ * Timer and hands it to launch_verify_votes.  One element each unless
+ * rf_mode() is on. */
+struct RfGather {
+    DevBuf pub, hm, ok;
+    explicit RfGather(size_t n)
+        : pub((rf_mode() ? n : 1) * sizeof(g1_t)), hm((rf_mode() ? n : 1) * sizeof(g2_t)),
+          ok((rf_mode() ? n : 1) * 4) {}
+    bool err() const { return pub.err || hm.err || ok.err; }
+};
+/* per-vote check against the key table: vote i is key d_idx[i] on hash point
+ * d_hm[d_hm_idx ? d_hm_idx[i] : i].  Above the threshold rf modes 1..3 go
+ * gather (keys and per-vote hash points) -> k_verify_rf. */
+static void launch_verify_votes(const g1aff_t *table, size_t n_keys, const uint32_t *d_idx,
+                                const g2_t *d_hm, const uint32_t *d_hm_idx,
+                                const g2aff_t *d_saff, const int32_t *d_sflags,
+                                const int32_t *d_hok, int32_t *d_res, size_t n,
+                                const RfGather &g) {
+    if (coop_wanted(n)) {
+        LAUNCH_COOP(k_verify_votes_coop, n, table, (int)n_keys, d_idx, d_hm, d_hm_idx,
+                    d_saff, d_sflags, d_hok, d_res, (int)n);
+        return;
+    }
+    int nb = scalar_blocks(n);
+#ifdef HBLS_RF
+    if (rf_mode() >= 1 && rf_mode() <= 3) {
+        hipLaunchKernelGGL(k_gather_votes_rf, dim3(nb), dim3(64), 0, 0,
+                           table, (int)n_keys, d_idx, d_hm, d_hm_idx, d_hok,
+                           g.pub.as<g1_t>(), g.hm.as<g2_t>(), g.ok.as<int32_t>(), (int)n);
+        hipLaunchKernelGGL(k_verify_rf, dim3(nb), dim3(64), 0, 0,
+                           g.pub.as<g1_t>(), g.hm.as<g2_t>(), d_saff, d_sflags,
+                           g.ok.as<int32_t>(), d_res, (int)n);
+        return;
+    }
+#endif
+    (void)g;
+    hipLaunchKernelGGL(k_verify_votes, dim3(nb), dim3(64), 0, 0,
+                       table, (int)n_keys, d_idx, d_hm, d_hm_idx, d_saff, d_sflags, d_hok,
+                       d_res, (int)n);
+}
 
 struct hbls_committee {
     g1aff_t *d_table;
@@ -2902,7 +2982,6 @@ static int run_agg_verify_pairing(const g1_t *d_agg, g2_t *d_hm, g2aff_t *d_saff
                                   size_t batch, const AggrlcPlan &plan, const EventSet<8> &ev,
                                   uint64_t t_launch, int32_t *results,
                                   AggrlcEarly *early = nullptr) {
-    int nb = (int)((batch + 63) / 64);
     (void)hipEventRecord(ev[6], 0);
     int arc = AGGRLC_FALLBACK;
     if (plan.combined) {
@@ -2911,10 +2990,8 @@ static int run_agg_verify_pairing(const g1_t *d_agg, g2_t *d_hm, g2aff_t *d_saff
     }
     if (arc == HBLS_OK) {
         /* combined path wrote every result */
-    } else if ((int)batch <= coop_threshold()) {
-        LAUNCH_COOP(k_verify_coop, batch, d_agg, d_hm, d_saff, d_sflags, d_hok, d_res,
-                    (int)batch);
-    } else if (rf_mode() == 0 && use_batch_affine()) {
+    } else if ((int)batch > coop_threshold() && rf_mode() == 0 && use_batch_affine()) {
+        /* exception: HBLS_BATCH_AFFINE is honoured here and by no other caller */
         DevBuf dpa(batch * sizeof(g1aff_t)), dpi(batch * 4), dha(batch * sizeof(g2aff_t));
         if (dpa.err || dpi.err || dha.err) return HBLS_ERR;
         int nba = (int)((batch + 64 * BA_K - 1) / (64 * BA_K));
@@ -2922,12 +2999,12 @@ static int run_agg_verify_pairing(const g1_t *d_agg, g2_t *d_hm, g2aff_t *d_saff
                            d_agg, dpa.as<g1aff_t>(), dpi.as<int32_t>(), (int)batch);
         hipLaunchKernelGGL(k_g2_batch_affine, dim3(nba), dim3(64), 0, 0,
                            d_hm, dha.as<g2aff_t>(), d_hok, (int)batch);
-        hipLaunchKernelGGL(k_verify_aff, dim3(nb), dim3(64), 0, 0,
+        hipLaunchKernelGGL(k_verify_aff, dim3(scalar_blocks(batch)), dim3(64), 0, 0,
                            dpa.as<g1aff_t>(), dpi.as<int32_t>(), dha.as<g2aff_t>(),
                            d_saff, d_sflags, d_hok, d_res, (int)batch);
         HIP_OK(hipDeviceSynchronize());   /* dpa/dha freed at scope exit */
     } else {
-        LAUNCH_VERIFY_SCALAR(nb, d_agg, d_hm, d_saff, d_sflags, d_hok, d_res, (int)batch);
+        launch_verify(d_agg, d_hm, d_saff, d_sflags, d_hok, d_res, batch);
     }
     (void)hipEventRecord(ev[7], 0);
     HIP_OK(hipEventSynchronize(ev[7]));
@@ -2972,7 +3049,6 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
     FreeClockArm farm(fclk);
     if (dagg.err || dhm.err || dsaff.err || dsflags.err || dhok.err || dres.err)
         return HBLS_ERR;
-    int nb = (int)((batch + 63) / 64);
     aggrlc_stats_reset();
     for (int i = 4; i < 9; i++) g_stage_ns[i] = 0;    /* the combined path's own, if it runs */
     /* ev[2s], ev[2s+1] around stage s (0 mask, 1 hash, 2 decompress, 3 verify) */
@@ -2983,26 +3059,12 @@ static int run_agg_verify_pipeline(const hbls_committee_t *c, const uint8_t *d_b
 
     if (src) HIP_OK(upload_then_wait((void *)d_msg, src->msgs, batch * msg_len, up[0]));
     (void)hipEventRecord(ev[2], 0);
-    if ((int)batch <= coop_threshold()) {
-        int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
-        LAUNCH_COOP(k_hash_to_g2_coop, batch, d_msg, (int)msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(),
-                           (int)batch, g_fast_cofactor);
-    } else {
-        hipLaunchKernelGGL(k_hash_to_g2, dim3(nb), dim3(64), 0, 0,
-                           d_msg, (int)msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(),
-                           (int)batch, g_fast_cofactor);
-    }
+    launch_hash_to_g2(d_msg, msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(), batch);
     (void)hipEventRecord(ev[3], 0);
 
     if (src) HIP_OK(upload_then_wait((void *)d_sig, src->sigs, batch * 96, up[1]));
     (void)hipEventRecord(ev[4], 0);
-    if ((int)batch <= coop_threshold()) {
-        int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
-        LAUNCH_COOP(k_g2_decompress_coop, batch, d_sig, dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
-    } else {
-        hipLaunchKernelGGL(k_g2_decompress, dim3(nb), dim3(64), 0, 0,
-                           d_sig, dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
-    }
+    launch_g2_decompress(d_sig, dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), batch);
     (void)hipEventRecord(ev[5], 0);
 
     /* the combined path's signature chain and chunk legs, ahead of and
@@ -3060,55 +3122,18 @@ extern "C" int hbls_batch_verify_votes(const hbls_committee_t *c, const uint32_t
     DevBuf didx(batch * 4), dsig(batch * 96), dmsg(batch * msg_len);
     DevBuf dhm(batch * sizeof(g2_t)), dsaff(batch * sizeof(g2aff_t));
     DevBuf dsflags(batch * 4), dhok(batch * 4), dres(batch * 4);
-    size_t gsz = rf_mode() ? batch : 1;   /* rf votes gather buffers */
-    DevBuf gpub(gsz * sizeof(g1_t)), ghm(gsz * sizeof(g2_t)), gok(gsz * 4);
+    RfGather rfg(batch);
     if (didx.err || dsig.err || dmsg.err || dhm.err || dsaff.err || dsflags.err ||
-        dhok.err || dres.err || gpub.err || ghm.err || gok.err) return HBLS_ERR;
+        dhok.err || dres.err || rfg.err()) return HBLS_ERR;
     HIP_OK(hipMemcpy(didx.p, key_idx, batch * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(dsig.p, sigs96, batch * 96, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(dmsg.p, msgs, batch * msg_len, hipMemcpyHostToDevice));
     Timer tm;
-    int nb = (int)((batch + 63) / 64);
-    if ((int)batch <= coop_threshold()) {
-        int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
-        LAUNCH_COOP(k_hash_to_g2_coop, batch, dmsg.as<uint8_t>(), (int)msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(),
-                           (int)batch, g_fast_cofactor);
-    } else {
-        hipLaunchKernelGGL(k_hash_to_g2, dim3(nb), dim3(64), 0, 0,
-                           dmsg.as<uint8_t>(), (int)msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(),
-                           (int)batch, g_fast_cofactor);
-    }
-    if ((int)batch <= coop_threshold()) {
-        int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
-        LAUNCH_COOP(k_g2_decompress_coop, batch, dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
-    } else {
-        hipLaunchKernelGGL(k_g2_decompress, dim3(nb), dim3(64), 0, 0,
-                           dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
-    }
-    if ((int)batch <= coop_threshold()) {
-        int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
-        LAUNCH_COOP(k_verify_votes_coop, batch, c->d_table, (int)c->n, didx.as<uint32_t>(), dhm.as<g2_t>(),
-                           (const uint32_t *)nullptr,
-                           dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), dhok.as<int32_t>(),
-                           dres.as<int32_t>(), (int)batch);
-    } else {
-#ifdef HBLS_RF
-        if (rf_mode() >= 1 && rf_mode() <= 3) {
-            LAUNCH_VOTES_SCALAR_RF(nb, c->d_table, (int)c->n, didx.as<uint32_t>(),
-                                   dhm.as<g2_t>(), (const uint32_t *)nullptr,
-                                   dsaff.as<g2aff_t>(), dsflags.as<int32_t>(),
-                                   dhok.as<int32_t>(), dres.as<int32_t>(), (int)batch,
-                                   gpub, ghm, gok, k_verify_rf);
-        } else
-#endif
-        {
-            hipLaunchKernelGGL(k_verify_votes, dim3(nb), dim3(64), 0, 0,
-                               c->d_table, (int)c->n, didx.as<uint32_t>(), dhm.as<g2_t>(),
-                               (const uint32_t *)nullptr,
-                               dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), dhok.as<int32_t>(),
-                               dres.as<int32_t>(), (int)batch);
-        }
-    }
+    launch_hash_to_g2(dmsg.as<uint8_t>(), msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(), batch);
+    launch_g2_decompress(dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), batch);
+    launch_verify_votes(c->d_table, c->n, didx.as<uint32_t>(), dhm.as<g2_t>(), nullptr,
+                        dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), dhok.as<int32_t>(),
+                        dres.as<int32_t>(), batch, rfg);
     tm.stop_and_store();
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(results, dres.p, batch * 4, hipMemcpyDeviceToHost));
@@ -3140,21 +3165,32 @@ extern "C" int hbls_verify_hash(const uint8_t pk48[48], const uint8_t sig96[96],
 }
 
 /* scalar G1/G2 ops */
-extern "C" int hbls_g1_add_impl(const uint8_t *a, const uint8_t *b, uint8_t *out, int sub) {
+/* the body of the single-point entries: upload one point of len bytes, or two
+ * (b), launch one thread, read its flag, and download the result (out) only
+ * when the flag is set; unset_rc is what an unset flag returns.  launch gets
+ * the device copies of a, b and out (null where there is none) and the flag. */
+template <typename Launch>
+static int run_point_op(const uint8_t *a, const uint8_t *b, uint8_t *out, size_t len,
+                        int unset_rc, Launch launch) {
     int rc = require_gpu();
     if (rc != HBLS_OK) return rc;
-    DevBuf da(48), db(48), dout(48), dok(4);
+    DevBuf da(len), db(len, b != nullptr), dout(len, out != nullptr), dok(4);
     if (da.err || db.err || dout.err || dok.err) return HBLS_ERR;
-    HIP_OK(hipMemcpy(da.p, a, 48, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(db.p, b, 48, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_g1_addsub, dim3(1), dim3(1), 0, 0,
-                       da.as<uint8_t>(), db.as<uint8_t>(), dout.as<uint8_t>(), dok.as<int32_t>(), sub);
+    HIP_OK(hipMemcpy(da.p, a, len, hipMemcpyHostToDevice));
+    if (b) HIP_OK(hipMemcpy(db.p, b, len, hipMemcpyHostToDevice));
+    launch(da.as<uint8_t>(), db.as<uint8_t>(), dout.as<uint8_t>(), dok.as<int32_t>());
     HIP_OK(hipDeviceSynchronize());
     int32_t ok;
     HIP_OK(hipMemcpy(&ok, dok.p, 4, hipMemcpyDeviceToHost));
-    if (!ok) return HBLS_ERR_BADINPUT;
-    HIP_OK(hipMemcpy(out, dout.p, 48, hipMemcpyDeviceToHost));
+    if (!ok) return unset_rc;
+    if (out) HIP_OK(hipMemcpy(out, dout.p, len, hipMemcpyDeviceToHost));
     return HBLS_OK;
+}
+extern "C" int hbls_g1_add_impl(const uint8_t *a, const uint8_t *b, uint8_t *out, int sub) {
+    return run_point_op(a, b, out, 48, HBLS_ERR_BADINPUT,
+                        [sub](uint8_t *da, uint8_t *db, uint8_t *dout, int32_t *dok) {
+        hipLaunchKernelGGL(k_g1_addsub, dim3(1), dim3(1), 0, 0, da, db, dout, dok, sub);
+    });
 }
 extern "C" int hbls_g1_add(const uint8_t a48[48], const uint8_t b48[48], uint8_t out48[48]) {
     return hbls_g1_add_impl(a48, b48, out48, 0);
@@ -3163,32 +3199,16 @@ extern "C" int hbls_g1_sub(const uint8_t a48[48], const uint8_t b48[48], uint8_t
     return hbls_g1_add_impl(a48, b48, out48, 1);
 }
 extern "C" int hbls_g2_add(const uint8_t a96[96], const uint8_t b96[96], uint8_t out96[96]) {
-    int rc = require_gpu();
-    if (rc != HBLS_OK) return rc;
-    DevBuf da(96), db(96), dout(96), dok(4);
-    if (da.err || db.err || dout.err || dok.err) return HBLS_ERR;
-    HIP_OK(hipMemcpy(da.p, a96, 96, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(db.p, b96, 96, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_g2_addsub, dim3(1), dim3(1), 0, 0,
-                       da.as<uint8_t>(), db.as<uint8_t>(), dout.as<uint8_t>(), dok.as<int32_t>(), 0);
-    HIP_OK(hipDeviceSynchronize());
-    int32_t ok;
-    HIP_OK(hipMemcpy(&ok, dok.p, 4, hipMemcpyDeviceToHost));
-    if (!ok) return HBLS_ERR_BADINPUT;
-    HIP_OK(hipMemcpy(out96, dout.p, 96, hipMemcpyDeviceToHost));
-    return HBLS_OK;
+    return run_point_op(a96, b96, out96, 96, HBLS_ERR_BADINPUT,
+                        [](uint8_t *da, uint8_t *db, uint8_t *dout, int32_t *dok) {
+        hipLaunchKernelGGL(k_g2_addsub, dim3(1), dim3(1), 0, 0, da, db, dout, dok, 0);
+    });
 }
 extern "C" int hbls_g1_check(const uint8_t p48[48]) {
-    int rc = require_gpu();
-    if (rc != HBLS_OK) return rc;
-    DevBuf dp(48), dok(4);
-    if (dp.err || dok.err) return HBLS_ERR;
-    HIP_OK(hipMemcpy(dp.p, p48, 48, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_g1_check, dim3(1), dim3(1), 0, 0, dp.as<uint8_t>(), dok.as<int32_t>());
-    HIP_OK(hipDeviceSynchronize());
-    int32_t ok;
-    HIP_OK(hipMemcpy(&ok, dok.p, 4, hipMemcpyDeviceToHost));
-    return ok ? HBLS_OK : HBLS_FALSE;
+    return run_point_op(p48, nullptr, nullptr, 48, HBLS_FALSE,
+                        [](uint8_t *dp, uint8_t *, uint8_t *, int32_t *dok) {
+        hipLaunchKernelGGL(k_g1_check, dim3(1), dim3(1), 0, 0, dp, dok);
+    });
 }
 extern "C" int hbls_g2_subgroup_methods(const uint8_t p96[96], int32_t out2[2]) {
     int rc = require_gpu();
@@ -3203,16 +3223,10 @@ extern "C" int hbls_g2_subgroup_methods(const uint8_t p96[96], int32_t out2[2]) 
     return HBLS_OK;
 }
 extern "C" int hbls_g2_check(const uint8_t p96[96]) {
-    int rc = require_gpu();
-    if (rc != HBLS_OK) return rc;
-    DevBuf dp(96), dok(4);
-    if (dp.err || dok.err) return HBLS_ERR;
-    HIP_OK(hipMemcpy(dp.p, p96, 96, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_g2_check, dim3(1), dim3(1), 0, 0, dp.as<uint8_t>(), dok.as<int32_t>());
-    HIP_OK(hipDeviceSynchronize());
-    int32_t ok;
-    HIP_OK(hipMemcpy(&ok, dok.p, 4, hipMemcpyDeviceToHost));
-    return ok ? HBLS_OK : HBLS_FALSE;
+    return run_point_op(p96, nullptr, nullptr, 96, HBLS_FALSE,
+                        [](uint8_t *dp, uint8_t *, uint8_t *, int32_t *dok) {
+        hipLaunchKernelGGL(k_g2_check, dim3(1), dim3(1), 0, 0, dp, dok);
+    });
 }
 
 /* round-1 per-thread double-and-add MSM, kept ONLY as the A/B reference for
@@ -4103,30 +4117,10 @@ extern "C" int hbls_batch_agg_verify_partials(
         hipLaunchKernelGGL(k_add_partials, dim3(nb), dim3(64), 0, 0,
                            dagg.as<g1_t>(), dext.as<uint8_t>(), (int)n_ext,
                            dpok.as<int32_t>(), (int)batch);
-    if ((int)batch <= coop_threshold()) {
-        int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
-        LAUNCH_COOP(k_hash_to_g2_coop, batch, dmsg.as<uint8_t>(), (int)msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(),
-                           (int)batch, g_fast_cofactor);
-    } else {
-        hipLaunchKernelGGL(k_hash_to_g2, dim3(nb), dim3(64), 0, 0,
-                           dmsg.as<uint8_t>(), (int)msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(),
-                           (int)batch, g_fast_cofactor);
-    }
-    if ((int)batch <= coop_threshold()) {
-        int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
-        LAUNCH_COOP(k_g2_decompress_coop, batch, dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
-    } else {
-        hipLaunchKernelGGL(k_g2_decompress, dim3(nb), dim3(64), 0, 0,
-                           dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
-    }
-    if ((int)batch <= coop_threshold()) {
-        int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
-        LAUNCH_COOP(k_verify_coop, batch, dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
-                           dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), (int)batch);
-    } else {
-        LAUNCH_VERIFY_SCALAR(nb, dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
-                           dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), (int)batch);
-    }
+    launch_hash_to_g2(dmsg.as<uint8_t>(), msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(), batch);
+    launch_g2_decompress(dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), batch);
+    launch_verify(dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
+                  dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), batch);
     if (n_ext)
         hipLaunchKernelGGL(k_merge_pok, dim3(nb), dim3(64), 0, 0,
                            dres.as<int32_t>(), dpok.as<int32_t>(), (int)batch);
@@ -4479,9 +4473,8 @@ extern "C" int hbls_stream_set_rounds(hbls_stream *s, const uint32_t *slots, int
     HIP_OK(hipMemcpy(dslots.p, slots, k * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(dpl.p, payloads, (size_t)k * plen, hipMemcpyHostToDevice));
     Timer tm;
-    int nbc = (k + CV_ITEMS - 1) / CV_ITEMS;
-    LAUNCH_COOP(k_hash_to_g2_coop, (size_t)k, dpl.as<uint8_t>(), (int)plen, dhm.as<g2_t>(), dok.as<int32_t>(),
-                       k, g_fast_cofactor);
+    /* exception: the cooperative hash whatever the threshold */
+    launch_hash_to_g2_coop(dpl.as<uint8_t>(), plen, dhm.as<g2_t>(), dok.as<int32_t>(), (size_t)k);
     hipLaunchKernelGGL(k_stream_scatter_hm, dim3((k + 63) / 64), dim3(64), 0, 0,
                        s->d_hm, s->d_hm_ok, dhm.as<g2_t>(), dok.as<int32_t>(),
                        dslots.as<uint32_t>(), k);
@@ -4513,11 +4506,9 @@ extern "C" int hbls_stream_process(hbls_stream *s, const uint32_t *key_idx,
     DevBuf dclamp(batch * 4), dpok(batch * 4);
     DevBuf dsaff(batch * sizeof(g2aff_t)), dsflags(batch * 4), dres(batch * 4);
     DevBuf dact(n_active * 4);
-    size_t gsz = rf_mode() ? batch : 1;   /* rf votes gather buffers */
-    DevBuf gpub(gsz * sizeof(g1_t)), ghm(gsz * sizeof(g2_t)), gok(gsz * 4);
+    RfGather rfg(batch);
     if (didx.err || dridx.err || dsig.err || dclamp.err || dpok.err ||
-        dsaff.err || dsflags.err || dres.err || dact.err ||
-        gpub.err || ghm.err || gok.err) return HBLS_ERR;
+        dsaff.err || dsflags.err || dres.err || dact.err || rfg.err()) return HBLS_ERR;
     HIP_OK(hipMemcpy(didx.p, key_idx, batch * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(dridx.p, round_idx, batch * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(dsig.p, sigs96, batch * 96, hipMemcpyHostToDevice));
@@ -4527,46 +4518,19 @@ extern "C" int hbls_stream_process(hbls_stream *s, const uint32_t *key_idx,
     hipLaunchKernelGGL(k_stream_clamp, dim3(nb), dim3(64), 0, 0,
                        dridx.as<uint32_t>(), s->max_rounds,
                        dclamp.as<uint32_t>(), dpok.as<int32_t>(), (int)batch);
+    launch_g2_decompress(dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), batch);
     if (s->verify_mode == 1) {
         /* batched: one pairing per round slot present in the tick, grouped
          * by the clamped round index (never by active_slots) */
-        if ((int)batch <= coop_threshold()) {
-            LAUNCH_COOP(k_g2_decompress_coop, batch, dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
-        } else {
-            hipLaunchKernelGGL(k_g2_decompress, dim3(nb), dim3(64), 0, 0,
-                               dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
-        }
         rc = rlc_verify_chain(s->c, s->d_hm, s->d_hm_ok, (size_t)s->max_rounds, round_idx,
                               didx.as<uint32_t>(), dclamp.as<uint32_t>(), dpok.as<int32_t>(),
                               dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), dres.as<int32_t>(),
                               batch);
         if (rc != HBLS_OK) { tm.stop_and_store(); return rc; }
-    } else if ((int)batch <= coop_threshold()) {
-        int nbc = (int)((batch + CV_ITEMS - 1) / CV_ITEMS);
-        LAUNCH_COOP(k_g2_decompress_coop, batch, dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
-        LAUNCH_COOP(k_verify_votes_coop, batch, s->c->d_table, (int)s->c->n, didx.as<uint32_t>(),
-                           s->d_hm, dclamp.as<uint32_t>(),
-                           dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), s->d_hm_ok,
-                           dres.as<int32_t>(), (int)batch);
     } else {
-        hipLaunchKernelGGL(k_g2_decompress, dim3(nb), dim3(64), 0, 0,
-                           dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), (int)batch);
-#ifdef HBLS_RF
-        if (rf_mode() >= 1 && rf_mode() <= 3) {
-            LAUNCH_VOTES_SCALAR_RF(nb, s->c->d_table, (int)s->c->n, didx.as<uint32_t>(),
-                                   s->d_hm, dclamp.as<uint32_t>(),
-                                   dsaff.as<g2aff_t>(), dsflags.as<int32_t>(),
-                                   s->d_hm_ok, dres.as<int32_t>(), (int)batch,
-                                   gpub, ghm, gok, k_verify_rf);
-        } else
-#endif
-        {
-            hipLaunchKernelGGL(k_verify_votes, dim3(nb), dim3(64), 0, 0,
-                               s->c->d_table, (int)s->c->n, didx.as<uint32_t>(),
-                               s->d_hm, dclamp.as<uint32_t>(),
-                               dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), s->d_hm_ok,
-                               dres.as<int32_t>(), (int)batch);
-        }
+        launch_verify_votes(s->c->d_table, s->c->n, didx.as<uint32_t>(), s->d_hm,
+                            dclamp.as<uint32_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(),
+                            s->d_hm_ok, dres.as<int32_t>(), batch, rfg);
     }
     hipLaunchKernelGGL(k_merge_pok, dim3(nb), dim3(64), 0, 0,
                        dres.as<int32_t>(), dpok.as<int32_t>(), (int)batch);
@@ -4607,14 +4571,8 @@ extern "C" int hbls_stream_check(hbls_stream *s, const uint32_t *slots, int k,
     launch_mask_aggregate(s->c->d_table, (int)s->c->n, dbm.as<uint8_t>(), (int)bm,
                           s->c->d_full_sum, dagg.as<g1_t>(), k,
                           s->c->d_wtab, s->c->d_winf);
-    if (k <= coop_threshold()) {
-        int nbc = (k + CV_ITEMS - 1) / CV_ITEMS;
-        LAUNCH_COOP(k_verify_coop, (size_t)k, dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
-                           dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), k);
-    } else {
-        LAUNCH_VERIFY_SCALAR((k + 63) / 64, dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
-                           dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), k);
-    }
+    launch_verify(dagg.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
+                  dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), (size_t)k);
     tm.stop_and_store();
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(ok, dres.p, k * 4, hipMemcpyDeviceToHost));
@@ -4646,8 +4604,9 @@ extern "C" int hbls_stream_check_submit(hbls_stream *s, const uint32_t *slots, i
     launch_mask_aggregate(s->c->d_table, (int)s->c->n, s->ck_bm, (int)bm,
                           s->c->d_full_sum, s->ck_agg, k,
                           s->c->d_wtab, s->c->d_winf, s->check_stream);
-    int nbc = (k + CV_ITEMS - 1) / CV_ITEMS;
-    hipLaunchKernelGGL(k_verify_coop<16>, dim3(nbc), dim3(64), 0, s->check_stream,
+    /* exception: always the 16-item cooperative kernel, on the check's own stream */
+    hipLaunchKernelGGL(k_verify_coop<16>, dim3((k + CV_ITEMS - 1) / CV_ITEMS), dim3(64), 0,
+                       s->check_stream,
                        s->ck_agg, s->ck_hm, s->ck_saff,
                        s->ck_sflags, s->ck_hok, s->ck_res, k);
     HIP_OK(hipGetLastError());

@@ -253,26 +253,15 @@ extern "C" int hbls_batch_verify_votes_multi(const hbls_committee_t *c,
     rc = mk_launch_sums(c, key_off, doff.as<uint32_t>(), didx.as<uint32_t>(), batch,
                         dsums.as<g1_t>(), dvok.as<int32_t>());
     if (rc != HBLS_OK) { tm.stop_and_store(); return rc; }
-    if ((int)batch <= coop_threshold()) {
-        LAUNCH_COOP(k_hash_to_g2_coop, batch, dmsg.as<uint8_t>(), (int)msg_len, dhm.as<g2_t>(),
-                    dhok.as<int32_t>(), (int)batch, g_fast_cofactor);
-        LAUNCH_COOP(k_g2_decompress_coop, batch, dsig.as<uint8_t>(), dsaff.as<g2aff_t>(),
-                    dsflags.as<int32_t>(), (int)batch);
-    } else {
-        hipLaunchKernelGGL(k_hash_to_g2, dim3(nb), dim3(64), 0, 0,
-                           dmsg.as<uint8_t>(), (int)msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(),
-                           (int)batch, g_fast_cofactor);
-        hipLaunchKernelGGL(k_g2_decompress, dim3(nb), dim3(64), 0, 0,
-                           dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(),
-                           (int)batch);
-    }
+    launch_hash_to_g2(dmsg.as<uint8_t>(), msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(), batch);
+    launch_g2_decompress(dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), batch);
     hipLaunchKernelGGL(k_mk_gather_hm, dim3(nb), dim3(64), 0, 0,
                        (const g2_t *)nullptr, (const uint32_t *)nullptr, dhok.as<int32_t>(),
                        (const int32_t *)nullptr, dvok.as<int32_t>(), (g2_t *)nullptr,
                        dhok.as<int32_t>(), (int)batch);
     /* the verify stage of run_agg_verify_pipeline, key sums for masked sums */
-    RLC_LAUNCH_CHECK(batch, dsums.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
-                     dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>());
+    launch_verify(dsums.as<g1_t>(), dhm.as<g2_t>(), dsaff.as<g2aff_t>(),
+                  dsflags.as<int32_t>(), dhok.as<int32_t>(), dres.as<int32_t>(), batch);
     tm.stop_and_store();
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(results, dres.p, batch * 4, hipMemcpyDeviceToHost));
@@ -331,14 +320,7 @@ extern "C" int hbls_stream_process_multi(hbls_stream *s, const uint32_t *key_off
     rc = mk_launch_sums(s->c, key_off, doff.as<uint32_t>(), didx.as<uint32_t>(), batch,
                         dsums.as<g1_t>(), dvok.as<int32_t>());
     if (rc != HBLS_OK) { tm.stop_and_store(); return rc; }
-    if ((int)batch <= coop_threshold()) {
-        LAUNCH_COOP(k_g2_decompress_coop, batch, dsig.as<uint8_t>(), dsaff.as<g2aff_t>(),
-                    dsflags.as<int32_t>(), (int)batch);
-    } else {
-        hipLaunchKernelGGL(k_g2_decompress, dim3(nb), dim3(64), 0, 0,
-                           dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(),
-                           (int)batch);
-    }
+    launch_g2_decompress(dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), batch);
     if (s->verify_mode == 1) {
         rc = rlc_verify_chain(s->c, s->d_hm, s->d_hm_ok, (size_t)s->max_rounds, round_idx,
                               (const uint32_t *)nullptr, dclamp.as<uint32_t>(),
@@ -349,8 +331,8 @@ extern "C" int hbls_stream_process_multi(hbls_stream *s, const uint32_t *key_off
         hipLaunchKernelGGL(k_mk_gather_hm, dim3(nb), dim3(64), 0, 0,
                            s->d_hm, dclamp.as<uint32_t>(), s->d_hm_ok, dpok.as<int32_t>(),
                            dvok.as<int32_t>(), ghm.as<g2_t>(), ghok.as<int32_t>(), (int)batch);
-        RLC_LAUNCH_CHECK(batch, dsums.as<g1_t>(), ghm.as<g2_t>(), dsaff.as<g2aff_t>(),
-                         dsflags.as<int32_t>(), ghok.as<int32_t>(), dres.as<int32_t>());
+        launch_verify(dsums.as<g1_t>(), ghm.as<g2_t>(), dsaff.as<g2aff_t>(),
+                      dsflags.as<int32_t>(), ghok.as<int32_t>(), dres.as<int32_t>(), batch);
     }
     hipLaunchKernelGGL(k_merge_pok, dim3(nb), dim3(64), 0, 0,
                        dres.as<int32_t>(), dpok.as<int32_t>(), (int)batch);

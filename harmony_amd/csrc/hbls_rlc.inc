@@ -304,16 +304,6 @@ static bool rlc_draw_scalars(uint64_t *out, size_t n) {
     return true;
 }
 
-/* pairing-check k prepared (P, hm, S) triples through the existing verify
- * chain, as hbls_stream_check does */
-#define RLC_LAUNCH_CHECK(k, dP, dhm, dsaff, dsflags, dhok, dres) do { \
-    if ((int)(k) <= coop_threshold()) { \
-        LAUNCH_COOP(k_verify_coop, (size_t)(k), dP, dhm, dsaff, dsflags, dhok, dres, (int)(k)); \
-    } else { \
-        LAUNCH_VERIFY_SCALAR((int)(((k) + 63) / 64), dP, dhm, dsaff, dsflags, dhok, dres, (int)(k)); \
-    } \
-} while (0)
-
 /* the batched verify chain.  Inputs are device-resident except h_grp, the
  * caller's raw group indices (host copy, for the counting sort):
  *   d_hm / d_hm_ok  n_groups hash points and their flags
@@ -411,8 +401,8 @@ static int rlc_verify_chain(const hbls_committee_t *c, const g2_t *d_hm,
                        d_hm, d_hm_ok, (int)n_groups,
                        gP.as<g1_t>(), ghm.as<g2_t>(), ghok.as<int32_t>(),
                        gsaff.as<g2aff_t>(), gsflags.as<int32_t>(), d_gcnt);
-    RLC_LAUNCH_CHECK(ng, gP.as<g1_t>(), ghm.as<g2_t>(), gsaff.as<g2aff_t>(),
-                     gsflags.as<int32_t>(), ghok.as<int32_t>(), d_gres);
+    launch_verify(gP.as<g1_t>(), ghm.as<g2_t>(), gsaff.as<g2aff_t>(),
+                  gsflags.as<int32_t>(), ghok.as<int32_t>(), d_gres, ng);
     HIP_OK(hipGetLastError());
     std::vector<int32_t> hg(2 * ng);
     HIP_OK(hipMemcpy(hg.data(), gout.p, 2 * ng * 4, hipMemcpyDeviceToHost));
@@ -446,8 +436,8 @@ static int rlc_verify_chain(const hbls_committee_t *c, const g2_t *d_hm,
                            dPA.as<g1_t>(), dPB.as<g2_t>(), d_hm, d_hm_ok, (int)n_groups,
                            cP.as<g1_t>(), chm.as<g2_t>(), chok.as<int32_t>(),
                            csaff.as<g2aff_t>(), csflags.as<int32_t>());
-        RLC_LAUNCH_CHECK(ns, cP.as<g1_t>(), chm.as<g2_t>(), csaff.as<g2aff_t>(),
-                         csflags.as<int32_t>(), chok.as<int32_t>(), cres.as<int32_t>());
+        launch_verify(cP.as<g1_t>(), chm.as<g2_t>(), csaff.as<g2aff_t>(),
+                      csflags.as<int32_t>(), chok.as<int32_t>(), cres.as<int32_t>(), ns);
         HIP_OK(hipGetLastError());
         std::vector<int32_t> hc(ns);
         HIP_OK(hipMemcpy(hc.data(), cres.p, ns * 4, hipMemcpyDeviceToHost));
@@ -511,25 +501,12 @@ extern "C" int hbls_batch_verify_votes_grouped(const hbls_committee_t *c,
     HIP_OK(hipMemcpy(dmsg.p, msgs, n_groups * msg_len, hipMemcpyHostToDevice));
     Timer tm;
     int nb = (int)((batch + 63) / 64);
-    if ((int)n_groups <= coop_threshold()) {
-        LAUNCH_COOP(k_hash_to_g2_coop, n_groups, dmsg.as<uint8_t>(), (int)msg_len,
-                    dhm.as<g2_t>(), dhok.as<int32_t>(), (int)n_groups, g_fast_cofactor);
-    } else {
-        hipLaunchKernelGGL(k_hash_to_g2, dim3((uint32_t)((n_groups + 63) / 64)), dim3(64), 0, 0,
-                           dmsg.as<uint8_t>(), (int)msg_len, dhm.as<g2_t>(),
-                           dhok.as<int32_t>(), (int)n_groups, g_fast_cofactor);
-    }
+    /* the hash dispatches on n_groups, the decompress on batch */
+    launch_hash_to_g2(dmsg.as<uint8_t>(), msg_len, dhm.as<g2_t>(), dhok.as<int32_t>(), n_groups);
     hipLaunchKernelGGL(k_stream_clamp, dim3(nb), dim3(64), 0, 0,
                        dgidx.as<uint32_t>(), (int)n_groups,
                        dclamp.as<uint32_t>(), dpok.as<int32_t>(), (int)batch);
-    if ((int)batch <= coop_threshold()) {
-        LAUNCH_COOP(k_g2_decompress_coop, batch, dsig.as<uint8_t>(), dsaff.as<g2aff_t>(),
-                    dsflags.as<int32_t>(), (int)batch);
-    } else {
-        hipLaunchKernelGGL(k_g2_decompress, dim3(nb), dim3(64), 0, 0,
-                           dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(),
-                           (int)batch);
-    }
+    launch_g2_decompress(dsig.as<uint8_t>(), dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), batch);
     rc = rlc_verify_chain(c, dhm.as<g2_t>(), dhok.as<int32_t>(), n_groups, group_idx,
                           didx.as<uint32_t>(), dclamp.as<uint32_t>(), dpok.as<int32_t>(),
                           dsaff.as<g2aff_t>(), dsflags.as<int32_t>(), dres.as<int32_t>(),
