@@ -166,6 +166,11 @@ def _load():
         lib.hbls_ctx_mask_sums.argtypes = [
             ctypes.c_void_p, u32p, ctypes.c_char_p, u32p, ctypes.c_size_t,
             ctypes.c_char_p, u64p, u32p, i32p]
+    # signed-message windows
+    if hasattr(lib, "hbls_batch_verify_msgs_ctx"):
+        lib.hbls_batch_verify_msgs_ctx.argtypes = [
+            ctypes.c_void_p, u32p, u32p, u32p, ctypes.c_char_p, u32p, ctypes.c_char_p,
+            u32p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, i32p]
     return lib
 
 
@@ -822,6 +827,44 @@ class ContextSet:
             out, pw, cn, ok), "ctx_mask_sums")
         return ([out.raw[48 * j:48 * (j + 1)] for j in range(batch)], list(pw), list(cn),
                 list(ok))
+
+    def verify_msgs(self, ctx_idx, key_lists, sigs: bytes, msg_idx, msgs, digest=None,
+                    csr=None):
+        """Single verifies over a window that mixes committees and messages
+        (DESIGN.md §4p): item j is sigs[96 * j:96 * (j + 1)] by the keys
+        key_lists[j] of committee ctx_idx[j] over msgs[msg_idx[j]].  msgs is a
+        list of byte strings of any lengths, each hashed to G2 once; where
+        digest[i] is true the message signed is keccak256(msgs[i]), computed on
+        the device.  Per item 1 accept, 0 reject, HBLS_ERR_BADINPUT (context or
+        message index out of range, malformed key list, undecodable signature,
+        a message that does not hash).  csr=(key_off, key_idx) replaces
+        key_lists, csr=(key_off, key_idx, msg_off) the message offsets too
+        (key_off None keeps key_lists); they are passed on as they are.  An
+        empty batch, an empty message table and offsets that do not start at 0
+        or that decrease raise BadInputError."""
+        if not hasattr(_lib, "hbls_batch_verify_msgs_ctx"):
+            raise HblsError("this libhbls.so has no signed-message entry: rebuild it")
+        batch = len(ctx_idx)
+        if len(sigs) != 96 * batch or len(msg_idx) != batch:
+            raise ValueError("ctx_idx/sigs/msg_idx length mismatch")
+        if digest is not None and len(digest) != len(msgs):
+            raise ValueError("digest must hold one flag per message")
+        key_csr = None if csr is None or csr[0] is None else (csr[0], csr[1])
+        off, idx, _ = _csr_arrays(key_lists, batch, key_csr)
+        mcat, moff = pack_blobs(msgs)
+        if csr is not None and len(csr) > 2:
+            moff = list(csr[2])
+            if len(moff) != len(msgs) + 1:
+                raise ValueError("msg_off must hold len(msgs) + 1 entries")
+            if max(moff) > len(mcat):
+                raise ValueError("msg_off points past the data")
+        flags = None if digest is None else bytes(1 if d else 0 for d in digest)
+        res = (ctypes.c_int32 * max(batch, 1))()
+        _check(_lib.hbls_batch_verify_msgs_ctx(
+            self._h, self._u32(ctx_idx, "ctx_idx"), off, idx, sigs,
+            self._u32(msg_idx, "msg_idx"), mcat, self._u32(moff, "msg_off"), len(msgs),
+            flags, batch, res), "batch_verify_msgs_ctx")
+        return list(res)[:batch]
 
     def __del__(self):
         try:

@@ -4391,6 +4391,7 @@ __global__ void k_stream_gather_check(const uint32_t *bitmap, int nwords, int bm
 #include "hbls_quorum.inc"
 #include "hbls_ctxset.inc"
 #include "hbls_multikey.inc"
+#include "hbls_msgs.inc"
 #include "hbls_probe.inc"
 
 extern "C" void hbls_stream_free(hbls_stream *s);

@@ -399,6 +399,39 @@ int hbls_stream_process_multi(hbls_stream_t *s, const uint32_t *key_off,
                               const uint8_t *sigs96, const uint32_t *active_slots,
                               int n_active, size_t batch, int32_t *results);
 
+/* ---- signed-message windows: mixed contexts, mixed messages ----
+ * hbls_batch_verify_votes_multi for a window whose items differ in committee
+ * and in message: the view-ID and view-change signatures of VIEWCHANGE
+ * messages (consensus/checks.go:186, view_change_construct.go:266,339), sender
+ * authentication over raw message bytes (consensus/checks.go:20-39), votes of
+ * several shards in one tick.
+ * Item j is signed by the keys key_idx[key_off[j] .. key_off[j+1]) of
+ * committee ctx_idx[j] (CSR form and rules of the multi-key entries) over
+ * entry msg_idx[j] of a message table.  Table entry i is
+ * msgs[msg_off[i] .. msg_off[i+1]), any length up to 2^31 - 1; when
+ * msg_digest is not NULL and msg_digest[i] != 0 the message signed is the
+ * Keccak-256 digest of those bytes (crypto/hash/hash.go:9-15), computed on the
+ * device.  Each entry is hashed to G2 once, however many items name it.
+ * results[j] is what hbls_verify_hash(K, sig_j, M) returns for the key sum K
+ * and the message M (bytes or digest), with the codes of
+ * hbls_batch_verify_votes_multi: herumi's identity edges included, an
+ * undecodable signature and a message that does not hash (the all-zero slot,
+ * which an empty undigested entry is) as that entry reports them.
+ * An item with ctx_idx[j] >= n_ctx, msg_idx[j] >= n_msgs, an empty list, an
+ * index >= n of its own committee or a list that is not strictly ascending is
+ * malformed: HBLS_ERR_BADINPUT as its own code, decided on the device before
+ * any of those values is used as an address; no key table is read for it and
+ * the other items keep their verdicts.
+ * The call fails with HBLS_ERR_BADINPUT before any upload on a NULL set or
+ * array, batch == 0, n_msgs == 0, key_off or msg_off that does not start at 0
+ * or decreases, more than 2^30 items or entries, more than 2^31 - 1 key
+ * indices or entry bytes, or more than 2^32 - 1 message bytes. */
+int hbls_batch_verify_msgs_ctx(const hbls_ctxset_t *s, const uint32_t *ctx_idx,
+                               const uint32_t *key_off, const uint32_t *key_idx,
+                               const uint8_t *sigs96, const uint32_t *msg_idx,
+                               const uint8_t *msgs, const uint32_t *msg_off, size_t n_msgs,
+                               const uint8_t *msg_digest, size_t batch, int32_t *results);
+
 /* ---- combined aggregate verify ----
  * How hbls_batch_agg_verify / hbls_batch_seal_verify run their pairing stage:
  *   0  exact: one final exponentiation per item
