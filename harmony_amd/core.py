@@ -152,6 +152,11 @@ def _load():
                                      ctypes.c_char_p, i32p]
     lib.hbls_arith_probe_op_name.argtypes = [ctypes.c_int]
     lib.hbls_arith_probe_op_name.restype = ctypes.c_char_p
+    # the stage probe: hash-to-G2 and G2 decompress per kernel variant
+    lib.hbls_hash_to_g2_probe.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t,
+                                          ctypes.c_int, ctypes.c_char_p, i32p]
+    lib.hbls_g2_decompress_probe.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int,
+                                             ctypes.c_char_p, i32p]
     # epoch contexts; guarded so that an older library loads
     if hasattr(lib, "hbls_ctxset_create"):
         lib.hbls_ctxset_create.restype = ctypes.c_void_p
@@ -491,6 +496,49 @@ def arith_probe(op: int, data: bytes, n_items: int, out_fp: int):
     flags = (ctypes.c_int32 * max(1, n_items))()
     _check(_lib.hbls_arith_probe(op, data, n_items, out, flags), "arith_probe")
     return out.raw[:n_items * out_fp * 48], list(flags)[:n_items]
+
+
+STAGE_KERNELS = ("scalar", "coop")      # the stage probe's kernel numbers 0 and 1
+
+
+def hash_to_g2_probe(msgs: bytes, mlen: int, batch: int, kernel: int):
+    """Test hook: hash batch messages of mlen bytes with
+    k_hash_to_g2 (kernel 0) or k_hash_to_g2_coop through its production
+    launcher (kernel 1), in the current cofactor mode.  Returns (batch x 96
+    serialized bytes, zero where ok is 0; the per-item ok flags)."""
+    if len(msgs) != mlen * batch:
+        raise ValueError("hash_to_g2_probe: %d bytes for %d x %d" % (len(msgs), batch, mlen))
+    out = ctypes.create_string_buffer(max(1, 96 * batch))
+    ok = (ctypes.c_int32 * max(1, batch))()
+    _check(_lib.hbls_hash_to_g2_probe(msgs, mlen, batch, kernel, out, ok), "hash_to_g2_probe")
+    return out.raw[:96 * batch], list(ok)[:batch]
+
+
+def g2_decompress_probe(sigs: bytes, batch: int, kernel: int):
+    """Test hook: decompress and subgroup-check batch
+    signatures with k_g2_decompress (kernel 0) or k_g2_decompress_coop
+    (kernel 1).  Returns (batch x 4 x 48 bytes, the affine x.a, x.b, y.a, y.b
+    as raw Montgomery limbs, meaningful where the flag is 1; the per-item
+    flags: 0 bad, 1 ok, 2 infinity)."""
+    if len(sigs) != 96 * batch:
+        raise ValueError("g2_decompress_probe: %d bytes for %d signatures" % (len(sigs), batch))
+    out = ctypes.create_string_buffer(max(1, 192 * batch))
+    flags = (ctypes.c_int32 * max(1, batch))()
+    _check(_lib.hbls_g2_decompress_probe(sigs, batch, kernel, out, flags),
+           "g2_decompress_probe")
+    return out.raw[:192 * batch], list(flags)[:batch]
+
+
+def hash_edge_count() -> int:
+    """items k_hash_to_g2_coop has sent down its exact scalar recompute since
+    the last reset (a degenerate addition in the cofactor chain, or the
+    full-cofactor mode); -1 if the counter cannot be read"""
+    return _lib.hbls_hash_edge_count()
+
+
+def hash_edge_reset():
+    if not _lib.hbls_hash_edge_reset():
+        raise HblsError("hash_edge_reset failed")
 
 
 def construct_commit_payload(block_num: int, hash32: bytes, view_id: int,

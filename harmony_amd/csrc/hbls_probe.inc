@@ -338,3 +338,69 @@ extern "C" int hbls_arith_probe(int op, const uint8_t *in, size_t n_items, uint8
     HIP_OK(hipMemcpy(flag, dflag.p, n_items * 4, hipMemcpyDeviceToHost));
     return HBLS_OK;
 }
+
+/* ---- stage probe: the two byte-to-point stages at the head of every verify
+ * pipeline, per kernel variant (DESIGN.md §4j).  kernel 0 is the
+ * thread-per-item kernel, kernel 1 the wave-cooperative one through the
+ * production launch path, whatever coop_threshold() says.  Per-item results
+ * come back uncollapsed, so tests/test_stage_probe_gpu.py can compare each
+ * item with the reference. */
+
+/* msgs: batch x msg_len bytes; out96: batch x 96 serialized hash points (zero
+ * bytes where ok is 0); ok: batch flags.  Honours hbls_set_g2_cofactor_mode. */
+extern "C" int hbls_hash_to_g2_probe(const uint8_t *msgs, size_t msg_len, size_t batch,
+                                     int kernel, uint8_t *out96, int32_t *ok) {
+    if (kernel < 0 || kernel > 1) return HBLS_ERR_BADINPUT;
+    if (!msgs || !out96 || !ok || msg_len == 0 || batch == 0 || batch > PROBE_MAX_ITEMS)
+        return HBLS_ERR_BADINPUT;
+    int rc = require_gpu();
+    if (rc != HBLS_OK) return rc;
+    DevBuf dm(batch * msg_len), dhm(batch * sizeof(g2_t)), dok(batch * 4), dser(batch * 96);
+    if (dm.err || dhm.err || dok.err || dser.err) return HBLS_ERR;
+    HIP_OK(hipMemcpy(dm.p, msgs, batch * msg_len, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(dok.p, 0xff, batch * 4));      /* an unwritten flag shows as -1 */
+    if (kernel == 1)
+        launch_hash_to_g2_coop(dm.as<uint8_t>(), msg_len, dhm.as<g2_t>(), dok.as<int32_t>(),
+                               batch);
+    else
+        hipLaunchKernelGGL(k_hash_to_g2, dim3(scalar_blocks(batch)), dim3(64), 0, 0,
+                           dm.as<uint8_t>(), (int)msg_len, dhm.as<g2_t>(), dok.as<int32_t>(),
+                           (int)batch, g_fast_cofactor);
+    hipLaunchKernelGGL(k_g2_serialize, dim3(scalar_blocks(batch)), dim3(64), 0, 0,
+                       dhm.as<g2_t>(), dser.as<uint8_t>(), dok.as<int32_t>(), (int)batch);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(out96, dser.p, batch * 96, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(ok, dok.p, batch * 4, hipMemcpyDeviceToHost));
+    return HBLS_OK;
+}
+
+/* sigs96: batch x 96 bytes; aff_out: batch x 4 fp raw Montgomery limbs
+ * (x.a, x.b, y.a, y.b), meaningful where the flag is 1 (the kernels may
+ * leave the other entries unwritten, so the buffer is cleared first);
+ * flags: 0 bad, 1 ok, 2 infinity. */
+extern "C" int hbls_g2_decompress_probe(const uint8_t *sigs96, size_t batch, int kernel,
+                                        uint8_t *aff_out, int32_t *flags) {
+    if (kernel < 0 || kernel > 1) return HBLS_ERR_BADINPUT;
+    if (!sigs96 || !aff_out || !flags || batch == 0 || batch > PROBE_MAX_ITEMS)
+        return HBLS_ERR_BADINPUT;
+    int rc = require_gpu();
+    if (rc != HBLS_OK) return rc;
+    DevBuf dsig(batch * 96), daff(batch * sizeof(g2aff_t)), dfl(batch * 4);
+    if (dsig.err || daff.err || dfl.err) return HBLS_ERR;
+    HIP_OK(hipMemcpy(dsig.p, sigs96, batch * 96, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(daff.p, 0, batch * sizeof(g2aff_t)));
+    HIP_OK(hipMemset(dfl.p, 0xff, batch * 4));
+    if (kernel == 1)
+        LAUNCH_COOP(k_g2_decompress_coop, batch, dsig.as<uint8_t>(), daff.as<g2aff_t>(),
+                    dfl.as<int32_t>(), (int)batch);
+    else
+        hipLaunchKernelGGL(k_g2_decompress, dim3(scalar_blocks(batch)), dim3(64), 0, 0,
+                           dsig.as<uint8_t>(), daff.as<g2aff_t>(), dfl.as<int32_t>(),
+                           (int)batch);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(aff_out, daff.p, batch * sizeof(g2aff_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(flags, dfl.p, batch * 4, hipMemcpyDeviceToHost));
+    return HBLS_OK;
+}

@@ -1,18 +1,29 @@
-"""GPU parity for the Fp2 square-root paths of the scalar (thread-per-item)
-kernels: k_hash_to_g2 (map candidates x1/x2/x3, both sqrt branches) and
-k_g2_decompress (both sqrt branches, both parities, root flipped or kept).
-The inputs are classified with the pure-Python oracle so that every path is
-shown to occur, not assumed to."""
+"""GPU parity for the Fp2 square-root paths of hash-to-G2 (map candidates
+x1/x2/x3, both sqrt branches) and of G2 decompress (both sqrt branches, both
+parities, root flipped or kept).  The inputs are classified with the
+pure-Python oracle (tests/stage_cases.py) so that every path is shown to
+occur, not assumed to.
+
+Which kernel each test reaches: test_hash_to_g2_all_paths runs k_hash_to_g2
+(hbls_batch_hash_to_g2 never takes the cooperative hash);
+test_g2_decompress_all_paths runs g2_deserialize inside k_g2_addsub through
+core.g2_add, and k_g2_decompress and k_g2_decompress_coop through the stage
+probe; test_g2_check_mutated_encodings runs k_g2_check.  The cooperative
+hash on the same payloads is in test_stage_probe_gpu.py."""
 import os
 import sys
 
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
+import arith_cases as ac  # noqa: E402
+import stage_cases as sc  # noqa: E402
 from oracle import pyref as pr  # noqa: E402
+from stage_cases import classify_map, classify_sig, sqrt_branch  # noqa: E402,F401
 
 
 def _gpu_available():
@@ -58,39 +69,6 @@ def sigs(capi, payloads):
     return [capi.sign_hash(sk_bytes(j), payloads[j]) for j in range(N)]
 
 
-def sqrt_branch(x):
-    """0: (a+w)/2 is the square; 1: (a-w)/2 is (pyref.f2_sqrt, b != 0 path)"""
-    a, b = x
-    assert b != 0
-    w = pr.fp_sqrt((a * a + b * b) % P)
-    assert w is not None
-    return 0 if pr.fp_sqrt((a + w) * INV2 % P) is not None else 1
-
-
-def g2_rhs(x):
-    return pr.f2_add(pr.f2_mul(pr.f2_sqr(x), x), pr.B2)
-
-
-def classify_map(msg):
-    """(candidate index, sqrt branch) that pyref.ft_map_g2 takes for msg"""
-    t2 = (pr.set_array_mask(msg), 0)
-    w = pr.f2_add(pr.f2_sqr(t2), pr.B2)
-    w = ((w[0] + 1) % P, w[1])
-    w = pr.f2_muls(pr.f2_mul(pr.f2_inv(w), t2), pr.FT_C1)
-    x1 = pr.f2_neg(pr.f2_mul(t2, w))
-    x1 = ((x1[0] + pr.FT_C2) % P, x1[1])
-    x2 = pr.f2_neg(x1)
-    x2 = ((x2[0] - 1) % P, x2[1])
-    x3 = pr.f2_inv(pr.f2_sqr(w))
-    x3 = ((x3[0] + 1) % P, x3[1])
-    for i, x in enumerate((x1, x2, x3)):
-        y2 = g2_rhs(x)
-        if pr.f2_sqrt(y2) is not None:
-            assert pr.ft_map_g2(t2)[0] == x
-            return i, sqrt_branch(y2)
-    raise AssertionError("no candidate")
-
-
 def test_hash_to_g2_all_paths(core, capi, payloads):
     cls = [classify_map(m) for m in payloads]
     cand = [sum(1 for c, _ in cls if c == i) for i in range(3)]
@@ -111,18 +89,6 @@ def test_hash_to_g2_all_paths(core, capi, payloads):
             capi.set_g2_cofactor_mode(True)
 
 
-def classify_sig(sig):
-    """(sqrt branch, encoded parity, root flipped) of one compressed point"""
-    odd = (sig[95] & 0x80) != 0
-    raw = bytearray(sig)
-    raw[95] &= 0x7F
-    x = (int.from_bytes(raw[:48], "little"), int.from_bytes(raw[48:], "little"))
-    y2 = g2_rhs(x)
-    y = pr.f2_sqrt(y2)
-    assert y is not None
-    return sqrt_branch(y2), int(odd), int(bool(pr.f2_is_odd(y)) != odd)
-
-
 def test_g2_decompress_all_paths(core, capi, sigs):
     cls = [classify_sig(s) for s in sigs]
     for k, name in enumerate(("sqrt branch", "parity", "root flipped")):
@@ -132,6 +98,15 @@ def test_g2_decompress_all_paths(core, capi, sigs):
     for k in range(N // 2):
         a, b = sigs[2 * k], sigs[2 * k + 1]
         assert core.g2_add(a, b) == capi.g2_add(a, b), k
+    # the decompress kernels themselves, thread-per-item and cooperative:
+    # flag and affine point of every signature against pyref.g2_deserialize
+    cases = sc.dec_valid_cases()
+    assert sigs == [c.sig for c in cases]
+    for kernel, name in enumerate(core.STAGE_KERNELS):
+        aff, flags = core.g2_decompress_probe(b"".join(sigs), N, kernel)
+        assert flags == [1] * N, name
+        for j, (c, got) in enumerate(zip(cases, ac.unpack(aff, 4))):
+            assert tuple(got) == sc.aff_limbs(c.point), (name, j)
 
 
 def test_g2_check_mutated_encodings(core, capi, sigs):
